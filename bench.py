@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: SEDT training throughput (audio clips/s) on synthetic batches, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dtype bf16|f32]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dtype bf16|f32] [--dump-outputs DIR]
 
 N > 1 without a launcher: this script starts N ranks ITSELF (``python -m torch.distributed.run`` as a child process,
 before the parent touches the GPU) and relays rank 0's JSON line.  Under a launcher (WORLD_SIZE set) it is one rank;
@@ -54,6 +54,10 @@ def parse():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernels', action='store_true', help='skip the per-kernel report')
     ap.add_argument('--dump-igemm', default=None, help='write per-launch igemm timings (json) to this path')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (losses / predictions) and a fixed sample of '
+                         'the parameters and gradients it left as DIR/<name>.npy (float32 / float64, at most 64 MB): two builds run '
+                         'with the same arguments see the same inputs and can be compared output for output')
     ap.add_argument('--host-matching', action='store_true',
                     help='c2/c3: solve the Hungarian matching on the host between two HIP graphs (the reference split)')
     ap.add_argument('--no-graph', action='store_true', help='c2/c3: issue every kernel from Python instead of replaying HIP graphs')
@@ -336,12 +340,12 @@ def build_workload(args, dev, rank, world):
 
             def step():
                 xb, tb = pf.next()
-                g(xb, tb)
+                return g(xb, tb)
         elif graphed:
             extras['stepper'] = g
 
             def step():
-                g(x, targets)
+                return g(x, targets)
         elif args.model_only:
             def step():
                 o = net(x)
@@ -349,10 +353,11 @@ def build_workload(args, dev, rank, world):
                     sum(a['pred_logits'].square().mean() + a['pred_boxes'].mean() for a in o['aux_outputs'])
                 loss.backward()
                 opt.zero_grad(set_to_none=True)
+                return o
         else:
             def step():
-                train_step(net, criterion, opt, x, targets, wm, slice(ns), max_norm=0.1, mix_up_ratio=mix,
-                           allreduce=bool(extras.get('eager_allreduce')))
+                return train_step(net, criterion, opt, x, targets, wm, slice(ns), max_norm=0.1, mix_up_ratio=mix,
+                                  allreduce=bool(extras.get('eager_allreduce')))
         extras.update(model=model, criterion=criterion, opt=opt, x=x, targets=targets, wm=wm, ns=ns, net=net)
         if graphed:
             def local_step():                     # the same step without the data-parallel schedule (exposed_comm)
@@ -379,7 +384,7 @@ def build_workload(args, dev, rank, world):
         extras.update(stepper=g, model=model)
 
         def step():
-            g(x, targets)
+            return g(x, targets)
         what = (f"validation body of engine.get_sedt_predictions, URBAN-SED SEDT enc_layers=3 dec_at num_queries=10 B={B}/GPU: no-grad "
                 f"forward + device matching + SetCriterion (logged losses) + audio tags + PostProcess (fusion strategy 1), one HIP graph")
         return step, B, FLOP_PER_CLIP['eval'] * B, what, True, extras
@@ -409,7 +414,7 @@ def build_workload(args, dev, rank, world):
         extras.update(stepper=g, model=model, targets=targets)
 
         def step():
-            g(x, targets, patches=patches)
+            return g(x, targets, patches=patches)
 
         def local_step():
             loc = GraphedTrainStep(model, criterion, opt, x, targets, slice(B), slice(B), max_norm=0.1, example_patches=patches,
@@ -465,7 +470,7 @@ def build_workload(args, dev, rank, world):
 
     def step():
         views()
-        g(x_t, x_s, targets)
+        return g(x_t, x_s, targets)
 
     def local_step():
         loc = GraphedSemiStep(model, ema, criterion, opt, x_t, x_s, targets, *masks, thr, mix_up_ratio=mix, data_parallel=False)
@@ -1024,6 +1029,63 @@ def other_configs(args, dev, keep_alive, replays=20, settle=30):
     return res
 
 
+DUMP_BUDGET = 64 << 20              # bytes, all arrays of one --dump-outputs together
+DUMP_MAX_ELEMS = 1 << 20            # elements per array; a larger one is written as a fixed, seeded sample of its flat elements
+
+
+def _dump_sample(t, cap, seed):
+    """t flattened; above `cap` elements a sorted sample drawn by a fixed seed (the same indices for the same numel in every run)"""
+    import numpy as np
+    import torch
+    flat = t.detach().reshape(-1)
+    if flat.numel() > cap:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), cap))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat
+
+
+def dump_outputs(out_dir, result, model, train):
+    """--dump-outputs: `result` is what the last timed step returned (nested dicts / lists / tuples of tensors); for a training
+    step also the parameters it updated and the gradients it computed, each as one flat sample over all trainable tensors (the
+    same indices in both).  Floating arrays are written as float32 (float64 stays), integer / bool ones as float64.  Returns {name: shape}"""
+    import re
+    import numpy as np
+    import torch
+    arrays = []
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            arrays.append((name, v.detach() if v.numel() <= DUMP_MAX_ELEMS else _dump_sample(v, DUMP_MAX_ELEMS, len(arrays))))
+        elif isinstance(v, dict):
+            for k in sorted(v, key=str):
+                walk(f'{name}.{k}', v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f'{name}.{i}', x)
+        elif isinstance(v, (bool, int, float)):
+            arrays.append((name, torch.tensor(v)))
+    walk('out', result)
+    if train:
+        ps = [p for p in model.parameters() if p.requires_grad]
+        arrays.append(('params', _dump_sample(torch.cat([p.detach().float().reshape(-1) for p in ps]), 2 * DUMP_MAX_ELEMS, 0)))
+        gs = [p.grad for p in ps if p.grad is not None]
+        if gs:
+            arrays.append(('grads', _dump_sample(torch.cat([g.detach().float().reshape(-1) for g in gs]), 2 * DUMP_MAX_ELEMS, 0)))
+    host = []
+    for name, t in arrays:
+        a = t.cpu()
+        a = a.numpy().astype(np.float64) if not a.is_floating_point() else \
+            a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        host.append((re.sub(r'[^A-Za-z0-9_.-]', '_', name), a))
+    total = sum(a.nbytes for _, a in host)
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f'--dump-outputs: {total} bytes, more than {DUMP_BUDGET >> 20} MB')
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host:
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in host}
+
+
 def pmc_traffic(config, stamp, kernels_per_step):
     """(profile dict or None, reason or None): HBM-side bytes per step from the committed PMC profile of this config (newest
     profiles/rNN_pmc_<config>.json) - but only when that profile was taken ON THIS BUILD: its `build_stamp` must equal the running
@@ -1096,13 +1158,19 @@ def main():
     barrier()
     settle_ms = {i: round(a_.elapsed_time(b_), 3) for i, (a_, b_) in settle_ev.items()}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    last = None
     t0 = time.perf_counter()
     e0.record()
     for _ in range(args.steps):
-        step()
+        last = step()
     e1.record()
     barrier()
     elapsed = time.perf_counter() - t0
+    # what the last timed step returned, before any further step overwrites the graphs' static outputs
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last, ex['model'], train=args.config != 'eval')
+    last = None
     # the host's own cost of ISSUING a step (table refresh, graph launches, RCCL enqueues): three steps queued onto an idle device - the
     # pinned upload rings have four slots, so the host does not block on the GPU inside this burst.  Every rank runs it (collectives match)
     t1 = time.perf_counter()
@@ -1275,6 +1343,8 @@ def main():
                # time the host spends ISSUING one step (table refresh, graph launches, RCCL enqueues; measured as a burst of three onto an idle device): while
                # this stays below ms_per_step the GPU never waits for the host; at N > 1 it tells exposed communication from host issue time
                "host_launch_us_per_step": round(host_issue * 1e6, 1)}
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if others is not None:
             out["other_configs"] = others
         if ex.get('graph_fallback'):
