@@ -27,6 +27,9 @@
  *   sedt_match_targets / sedt_hungarian_batch                                 HungarianMatcher      sedt/matcher.py:41-133
  *   sedt_set_criterion(_bwd) / sedt_feature_loss                              SetCriterion          sedt/sedt.py:134-352
  *   sedt_postprocess / sedt_pseudo_labels                                     PostProcess, get_pseudo_labels  sedt/sedt.py:355-396, engine.py:300-348
+ *   sedt_event_metrics_update                                                 decode_strong + sed_eval event-based / clip-level counts
+ *                                                                             utilities/BoxEncoder.py:179-226, engine.py:199-297,
+ *                                                                             utilities/metrics.py:43-80, 281-322
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -729,6 +732,32 @@ int sedt_postprocess(const float* logits, const float* boxes, const float* tags,
 int sedt_pseudo_labels(const float* logits, const float* boxes, const float* at, const float* thr, float min_len, int B,
                        int Q, int C, int del_overlap, int64_t* lab_cat, float* box_cat, int32_t* lab_off, int32_t* box_off,
                        int32_t* counter, int cap, void* stream);
+
+/* ------------------------------------------------------------------ validation scores on the device
+ * sedt_event_metrics_update (engine.py:199-297 with utilities/BoxEncoder.py:179-226 and utilities/metrics.py:43-80, 281-322): one
+ * wave per clip of one fusion strategy's PostProcess outputs (scores [B][Q] f32, labels [B][Q] int64, boxes [B][Q][2] f32 seconds).
+ * Decode (decode_strong): a query is kept when score >= threshold (del_overlap) or score > threshold (!del_overlap) and
+ * offset - onset >= min_duration, both in f32; with del_overlap the kept events of a class are ordered by onset (ties: lower query
+ * first) and swept once: an event starting before the end of the last one still standing replaces it when its score is strictly
+ * higher, else is dropped.  Onsets / offsets are then clipped to [0, max_len] and compared in float64 with the clip's reference
+ * events: a hit is same class, |on_r - on_e| <= t_collar and |off_r - off_e| <= max(t_collar, pct * (off_r - on_r)).  Per class,
+ * tp = the maximum-cardinality matching of the hits (optimal != 0, sed_eval's 'optimal') or sed_eval's greedy pass (references in
+ * table order, estimates in decoded order).
+ * Reference table (uploaded once per validation set): clip k owns events [ref_off[k], ref_off[k+1]) of ref_cls (int32 class),
+ * ref_on / ref_end (float64 seconds); ref_present [n_clips] int32 (null = all 1): 0 for a clip that has no row in the reference;
+ * max_ref = the largest event count of a clip (<= 64).  clip_idx [B] int32: the batch's clips in the table, -1 (or >= n_clips) for a
+ * clip outside it (treated like ref_present 0).
+ * Counters (int64, accumulated with integer atomics; zero them per validation set):
+ *   ev_counts  [n_fusion][C][3] += {tp, n_ref, n_sys} at row `fusion`, from clips in the reference only (metrics.py:58);
+ *   tag_counts [n_fusion + 1][C][3] += {tp, fp, fn} of "class among the decoded events" vs "class among the reference events" at
+ *   row `fusion`, from every clip (the outer merge of metrics.py:289); with at_tags [B][C] (int64 0/1, may be null) the same counts
+ *   of the audio-tag head at row n_fusion.  Q <= 64, C <= 63. */
+int sedt_event_metrics_update(const float* scores, const int64_t* labels, const float* boxes, const int64_t* at_tags,
+                              const int32_t* clip_idx, const int32_t* ref_present, const int32_t* ref_off, const int32_t* ref_cls,
+                              const double* ref_on,
+                              const double* ref_end, int n_clips, int max_ref, int B, int Q, int C, int n_fusion, int fusion,
+                              float threshold, float min_duration, double max_len, double t_collar, double pct, int del_overlap,
+                              int optimal, int64_t* ev_counts, int64_t* tag_counts, void* stream);
 
 /* ------------------------------------------------------------------ input side on the device (utilities/BoxTransforms.py,
  * utilities/mixup.py)

@@ -1,0 +1,213 @@
+// metrics.hip - validation scores on the device: the per-clip part of reference engine.get_sedt_predictions + utilities/metrics.py
+//   * event_metrics_kernel   BoxEncoder.decode_strong (utilities/BoxEncoder.py:179-226) + the clip to [0, max_len] (engine.py:287)
+//                            + sed_eval EventBasedMetrics counts (metrics.py:43-80: t_collar, percentage_of_length, onset and offset)
+//                            + clip-level tag counts of the decoded events and of the audio-tag head (metrics.py:281-322)
+// One wave per clip.  The decode runs in f32 on PostProcess's f32 values, exactly as the reference's numpy / torch scalars do; the
+// matching conditions run in float64 on those values, as sed_eval compares Python floats.  Counts land in int64 counters through
+// integer atomics only: every result is independent of the order the clips arrive in.
+#include "common.h"
+
+#pragma clang fp contract(off)     // the float64 collar tests must be the plain sub / mul / compare sed_eval evaluates
+
+namespace sedt {
+
+#define SEDT_EM_MAXQ 64            // queries per clip (one lane each)
+#define SEDT_EM_MAXC 63            // classes (one lane each in the per-class passes)
+#define SEDT_EM_MAXR 64            // reference events per clip (one bit row of the hit graph each)
+
+// ---------------------------------------------------------------------------------------------------------------------
+// block = 64 threads = one wave, blockIdx.x = clip of the batch.
+//   ev  [n_fusion][C][3] += {tp, n_ref, n_sys}       (only clips that are in the reference: clip_idx >= 0)
+//   tag [n_fusion + 1][C][3] += {tp, fp, fn}         (every clip: reference clips and clips without any reference row alike)
+__global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restrict__ scores, const int64_t* __restrict__ labels,
+                                                           const float* __restrict__ boxes, const int64_t* __restrict__ at_tags,
+                                                           const int32_t* __restrict__ clip_idx, const int32_t* __restrict__ ref_present,
+                                                           const int32_t* __restrict__ ref_off,
+                                                           const int32_t* __restrict__ ref_cls, const double* __restrict__ ref_on,
+                                                           const double* __restrict__ ref_end, int n_clips, int Q, int C, int n_fusion,
+                                                           int fusion, float threshold, float min_dur, double max_len, double t_collar,
+                                                           double pct, int del_overlap, int optimal, unsigned long long* __restrict__ ev,
+                                                           unsigned long long* __restrict__ tag) {
+  __shared__ float s_on[SEDT_EM_MAXQ], s_end[SEDT_EM_MAXQ], s_score[SEDT_EM_MAXQ];
+  __shared__ int s_lab[SEDT_EM_MAXQ], s_keep[SEDT_EM_MAXQ], s_surv[SEDT_EM_MAXQ], s_order[SEDT_EM_MAXQ];
+  __shared__ int r_cls[SEDT_EM_MAXR];
+  __shared__ double r_on[SEDT_EM_MAXR], r_end[SEDT_EM_MAXR];
+  __shared__ unsigned long long adj[SEDT_EM_MAXR];                  // adj[j] bit q: estimate q hits reference j
+  __shared__ int match_est[SEDT_EM_MAXQ], from_ref[SEDT_EM_MAXQ], match_ref[SEDT_EM_MAXR];
+  __shared__ unsigned char queue[SEDT_EM_MAXC][SEDT_EM_MAXR];       // BFS queue of class c (refs of one class, one clip)
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int clip = clip_idx[b];
+  if (clip >= n_clips || (clip >= 0 && ref_present && !ref_present[clip])) clip = -1;   // not in the reference (the host validates)
+  int e0 = 0, ne = 0;
+  if (clip >= 0) {
+    e0 = ref_off[clip];
+    ne = min(ref_off[clip + 1] - e0, SEDT_EM_MAXR);                  // sedt_event_metrics_update checks the table on the host
+  }
+
+  // ---- decode_strong: keep, then order by (class, onset, query) with del_overlap / (class, query) without
+  float on = 0.f, end = 0.f, sc = -INFINITY;
+  int lab = 0;
+  bool keep = false;
+  if (lane < Q) {
+    const long r = (long)b * Q + lane;
+    sc = scores[r];
+    lab = (int)labels[r];
+    on = boxes[2 * r];
+    end = boxes[2 * r + 1];
+    const bool pass = del_overlap ? (sc >= threshold) : (sc > threshold);   // BoxEncoder.py:203 / :190
+    keep = pass && (end - on) >= min_dur && lab >= 0 && lab < C;
+  }
+  int pos = 0;
+  for (int j = 0; j < Q; ++j) {
+    const int kj = __shfl((int)keep, j, 64), lj = __shfl(lab, j, 64);
+    const float oj = __shfl(on, j, 64);
+    const bool before = lj < lab || (lj == lab && (del_overlap ? (oj < on || (oj == on && j < lane)) : j < lane));
+    pos += (kj && before) ? 1 : 0;
+  }
+  if (lane < SEDT_EM_MAXQ) {
+    s_on[lane] = on; s_end[lane] = end; s_score[lane] = sc; s_lab[lane] = lab;
+    s_keep[lane] = keep; s_surv[lane] = keep;
+    match_est[lane] = -1;
+  }
+  if (keep) s_order[pos] = lane;
+  for (int j = lane; j < ne; j += 64) {
+    r_cls[j] = ref_cls[e0 + j];
+    r_on[j] = ref_on[e0 + j];
+    r_end[j] = ref_end[e0 + j];
+    match_ref[j] = -1;
+  }
+  __syncthreads();
+
+  // per class (lane c): its run [start, start + n) of s_order
+  const int c = lane;
+  int start = 0, n_c = 0;
+  if (c < C)
+    for (int j = 0; j < Q; ++j)
+      if (s_keep[j]) {
+        start += s_lab[j] < c;
+        n_c += s_lab[j] == c;
+      }
+  // ---- sequential same-class overlap removal in onset order (BoxEncoder.py:212-223): an event overlapping the last one still
+  // standing removes it when its score is strictly higher, else is removed itself
+  if (del_overlap && c < C && n_c > 1) {
+    int top = s_order[start];
+    for (int k = 1; k < n_c; ++k) {
+      const int q = s_order[start + k];
+      if (s_on[q] < s_end[top]) {
+        if (s_score[q] > s_score[top]) {
+          s_surv[top] = 0;
+          top = q;
+        } else {
+          s_surv[q] = 0;
+        }
+      } else {
+        top = q;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- hit graph: same class, |on_r - on_e| <= collar, |off_r - off_e| <= max(collar, pct * (off_r - on_r)), in float64 on the
+  // estimates clipped to [0, max_len] (engine.py:287)
+  const bool surv = lane < Q && s_surv[lane];
+  const double my_on = fmin(fmax((double)on, 0.0), max_len), my_end = fmin(fmax((double)end, 0.0), max_len);
+  for (int j = 0; j < ne; ++j) {
+    const double ron = r_on[j], rend = r_end[j];
+    const double off_collar = fmax(t_collar, pct * (rend - ron));
+    const bool hit = surv && lab == r_cls[j] && fabs(ron - my_on) <= t_collar && fabs(rend - my_end) <= off_collar;
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) adj[j] = m;
+  }
+  __syncthreads();
+
+  // ---- per class: tp = maximum-cardinality matching (augmenting paths, breadth first) or sed_eval's greedy pass
+  long tp = 0, n_ref = 0, n_sys = 0;
+  if (c < C) {
+    for (int k = 0; k < n_c; ++k) n_sys += s_surv[s_order[start + k]];
+    for (int j = 0; j < ne; ++j) {
+      if (r_cls[j] != c) continue;
+      ++n_ref;
+      if (adj[j] == 0ull) continue;
+      if (optimal) {
+        unsigned char* qu = queue[c];
+        int head = 0, tail = 0, found = -1;
+        unsigned long long seen = 0ull;
+        qu[tail++] = (unsigned char)j;
+        while (head < tail && found < 0) {
+          const int r = qu[head++];
+          unsigned long long avail = adj[r] & ~seen;
+          while (avail) {
+            const int q = __ffsll((long long)avail) - 1;
+            avail &= avail - 1ull;
+            seen |= 1ull << q;
+            from_ref[q] = r;
+            if (match_est[q] < 0) { found = q; break; }
+            qu[tail++] = (unsigned char)match_est[q];    // each matched ref enters once: its estimate is seen once
+          }
+        }
+        if (found >= 0) {
+          int q = found;
+          for (;;) {                                      // flip the path back to j
+            const int r = from_ref[q], prev = match_ref[r];
+            match_ref[r] = q;
+            match_est[q] = r;
+            if (r == j) break;
+            q = prev;
+          }
+          ++tp;
+        }
+      } else {
+        for (int k = 0; k < n_c; ++k) {                   // estimates in their output order, first free hit wins
+          const int q = s_order[start + k];
+          if (s_surv[q] && match_est[q] < 0 && ((adj[j] >> q) & 1ull)) {
+            match_est[q] = j;
+            ++tp;
+            break;
+          }
+        }
+      }
+    }
+    if (clip >= 0) {
+      unsigned long long* e = ev + ((long)fusion * C + c) * 3;
+      if (tp) atomicAdd(e, (unsigned long long)tp);
+      if (n_ref) atomicAdd(e + 1, (unsigned long long)n_ref);
+      if (n_sys) atomicAdd(e + 2, (unsigned long long)n_sys);
+    }
+    // ---- clip level: class present among the decoded events / among the reference events / among the audio tags
+    const bool ref_has = n_ref > 0, sys_has = n_sys > 0;
+    unsigned long long* t = tag + ((long)fusion * C + c) * 3;
+    if (ref_has && sys_has) atomicAdd(t, 1ull);
+    if (!ref_has && sys_has) atomicAdd(t + 1, 1ull);
+    if (ref_has && !sys_has) atomicAdd(t + 2, 1ull);
+    if (at_tags) {
+      const bool at_has = at_tags[(long)b * C + c] != 0;
+      unsigned long long* a = tag + ((long)n_fusion * C + c) * 3;
+      if (ref_has && at_has) atomicAdd(a, 1ull);
+      if (!ref_has && at_has) atomicAdd(a + 1, 1ull);
+      if (ref_has && !at_has) atomicAdd(a + 2, 1ull);
+    }
+  }
+}
+
+}  // namespace sedt
+
+extern "C" int sedt_event_metrics_update(const float* scores, const int64_t* labels, const float* boxes, const int64_t* at_tags,
+                                         const int32_t* clip_idx, const int32_t* ref_present, const int32_t* ref_off,
+                                         const int32_t* ref_cls, const double* ref_on,
+                                         const double* ref_end, int n_clips, int max_ref, int B, int Q, int C, int n_fusion, int fusion,
+                                         float threshold, float min_duration, double max_len, double t_collar, double pct,
+                                         int del_overlap, int optimal, int64_t* ev_counts, int64_t* tag_counts, void* stream) {
+  using namespace sedt;
+  SEDT_REQUIRE(scores && labels && boxes && clip_idx && ref_off && ev_counts && tag_counts, "event_metrics_update: null pointer");
+  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_EM_MAXQ && C >= 1 && C <= SEDT_EM_MAXC, "event_metrics_update: B=%d Q=%d (<=%d) C=%d (<=%d)",
+               B, Q, SEDT_EM_MAXQ, C, SEDT_EM_MAXC);
+  SEDT_REQUIRE(n_clips >= 0 && (n_clips == 0 || (ref_cls && ref_on && ref_end)), "event_metrics_update: reference table missing");
+  SEDT_REQUIRE(max_ref >= 0 && max_ref <= SEDT_EM_MAXR, "event_metrics_update: a clip has %d reference events (<= %d)", max_ref,
+               SEDT_EM_MAXR);
+  SEDT_REQUIRE(n_fusion >= 1 && fusion >= 0 && fusion < n_fusion, "event_metrics_update: fusion %d of %d", fusion, n_fusion);
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(event_metrics_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), scores, labels, boxes, at_tags,
+                     clip_idx, ref_present, ref_off, ref_cls, ref_on, ref_end, n_clips, Q, C, n_fusion, fusion, threshold, min_duration, max_len,
+                     t_collar, pct, del_overlap, optimal, reinterpret_cast<unsigned long long*>(ev_counts),
+                     reinterpret_cast<unsigned long long*>(tag_counts));
+  return check_launch("event_metrics_update");
+}

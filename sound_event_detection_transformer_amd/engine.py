@@ -651,12 +651,14 @@ def _tensors(x):
 
 
 # ---------------------------------------------------------------------------------------------------- validation / prediction
-def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_strategy=(1,), at=True, threshold=0.5):
+def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_strategy=(1,), at=True, threshold=0.5, metrics=None,
+                 clip_idx=None):
     """The per-batch body of reference engine.get_sedt_predictions (engine.py:244-285) on the device: no-grad forward, the
     losses the reference logs (criterion with strong_mask = the whole batch), the thresholded audio tags, and
     ``postprocessors['bbox']`` once per fusion strategy.  Returns (loss_dict, audio_tags or None, {at_m: (scores [B,Q], labels
-    [B,Q], boxes [B,Q,2] in seconds)}); the host-side decoding into event lists (decoder.decode_strong, pandas) stays the
-    caller's, as in the reference."""
+    [B,Q], boxes [B,Q,2] in seconds)}).  With ``metrics`` (utilities.metrics.EventMetrics) the decode and the event-based /
+    clip-level counts of the batch (clips ``clip_idx`` of the metrics' reference) are added on the device as well; without it
+    the decoding into event lists stays the caller's, as in the reference."""
     with torch.no_grad():
         outputs = model(batch_input)
         B = outputs['pred_logits'].shape[0]
@@ -666,17 +668,31 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
         if at:
             assert 'at' in outputs
         results = {m: postprocessor.batched(outputs, sizes, audio_tags=audio_tags, at_m=m, threshold=threshold) for m in fusion_strategy}
+        if metrics is not None:
+            _check_metrics(metrics, fusion_strategy)
+            if clip_idx is None:
+                raise ValueError('predict_step(metrics=...) needs the clip indices of the batch (clip_idx)')
+            metrics.update(results, audio_tags, clip_idx)
     return loss_dict, audio_tags, results
+
+
+def _check_metrics(metrics, fusion_strategy):
+    if tuple(fusion_strategy) != metrics.fusion:
+        raise ValueError(f'EventMetrics counts fusion strategies {metrics.fusion}, the predict step runs {tuple(fusion_strategy)}')
 
 
 class GraphedPredictStep(object):
     """predict_step as ONE HIP graph (forward, device Hungarian matching + fused losses for the logged validation losses, audio
     tags, PostProcess for every fusion strategy): per batch the host refreshes the static input / target tables and replays;
     the outputs are static tensors (overwritten by the next call).  Shapes are static like GraphedTrainStep's.  Weight packs
-    follow parameter-pointer swaps (an EMA teacher evaluated through ``ema.apply_shadow()`` gets its own pack plan)."""
+    follow parameter-pointer swaps (an EMA teacher evaluated through ``ema.apply_shadow()`` gets its own pack plan).
+
+    ``metrics`` (utilities.metrics.EventMetrics, its reference set before the step is built): the graph also decodes every clip
+    and adds the event-based / clip-level counts to the metrics' device counters; each call then takes the batch's clip indices,
+    and a validation epoch is N replays and one ``metrics.compute()``.  Building the step leaves the counters as they were."""
 
     def __init__(self, model, criterion, postprocessor, example_input, example_targets, fusion_strategy=(1,), at=True, threshold=0.5,
-                 max_targets=32, warmup=2):
+                 max_targets=32, warmup=2, metrics=None):
         from .sedt import TargetTables
         self.model, self.criterion, self.post = model, criterion, postprocessor
         self.fusion, self.at, self.threshold = tuple(fusion_strategy), at, threshold
@@ -685,6 +701,14 @@ class GraphedPredictStep(object):
         B = len(example_targets)
         self.tables = TargetTables(B, B, B, dev, max_targets=max_targets, with_ratio=False, weak_mask_none=True).load(example_targets)
         self.sizes = torch.stack([t['orig_size'] for t in example_targets], dim=0).to(dev).float().clone()
+        self.metrics = metrics
+        if metrics is not None:
+            _check_metrics(metrics, self.fusion)
+            if metrics.table is None:
+                raise RuntimeError('GraphedPredictStep(metrics=...): call metrics.set_reference() before building the step')
+            self.clip_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            self.metrics_gen = metrics.generation
+            saved = (metrics.ev.clone(), metrics.tag.clone())          # the warm-up runs count too: put the counters back after
         stream = train_stream(dev)
         stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(stream):
@@ -692,6 +716,10 @@ class GraphedPredictStep(object):
                 self._body()
         torch.cuda.current_stream().wait_stream(stream)
         torch.cuda.synchronize()
+        if metrics is not None:
+            metrics.ev.copy_(saved[0])
+            metrics.tag.copy_(saved[1])
+            torch.cuda.synchronize()
         quiesce_collectives(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=stream, **_CAPTURE):
@@ -705,14 +733,44 @@ class GraphedPredictStep(object):
             losses = self.criterion.compute(outputs, dense)
             tags = (outputs['at'] > 0.5).long() if self.at else None
             res = {m: self.post.batched(outputs, self.sizes, audio_tags=tags, at_m=m, threshold=self.threshold) for m in self.fusion}
+            if self.metrics is not None:
+                self.metrics.update(res, tags, self.clip_idx)
         return losses, tags, res
 
-    def __call__(self, batch_input, targets):
+    def __call__(self, batch_input, targets, clip_idx=None):
         self.static_x.copy_(batch_input, non_blocking=True)
         self.tables.load(targets)
         self.sizes.copy_(torch.stack([t['orig_size'] for t in targets], dim=0), non_blocking=True)
+        if self.metrics is not None:
+            if clip_idx is None:
+                raise ValueError('GraphedPredictStep(metrics=...) needs the clip indices of the batch (clip_idx)')
+            if self.metrics.generation != self.metrics_gen:
+                raise RuntimeError('GraphedPredictStep: the metrics\' reference changed shape after the step was built; build a new step')
+            if not (torch.is_tensor(clip_idx) and clip_idx.is_cuda):
+                clip_idx = self.metrics.host_clip_index(clip_idx)
+            self.clip_idx.copy_(clip_idx, non_blocking=True)
         self.graph.replay()
         return self.out
+
+
+def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, threshold=0.5, graphed=True, max_targets=32):
+    """engine.evaluate (engine.py:199-216) without leaving the device: ``batches`` yields (input, targets, clip indices into the
+    metrics' reference) - the reference's data_prefetcher gives ((input, targets), indexes).  The counters are reset, every batch
+    goes through one GraphedPredictStep(metrics=...) replay (a batch of another size, such as a short last one, through the eager
+    predict_step with the same kernels), and the scores are read back once: returns ``metrics.compute()``, whose
+    [at_m]['f1'] is the event-based macro F1 the reference's evaluate returns as metrics[at_m]."""
+    metrics.reset()
+    step = None
+    for x, targets, idx in batches:
+        if graphed and step is None:
+            step = GraphedPredictStep(model, criterion, postprocessor, x, targets, fusion_strategy=metrics.fusion, at=at,
+                                      threshold=threshold, max_targets=max_targets, metrics=metrics)
+        if step is not None and x.shape == step.static_x.shape:
+            step(x, targets, idx)
+        else:
+            predict_step(model, criterion, postprocessor, x, targets, fusion_strategy=metrics.fusion, at=at, threshold=threshold,
+                         metrics=metrics, clip_idx=idx)
+    return metrics.compute()
 
 
 def pseudo_label_tables(tea_outputs, classwise_threshold, orig_size, tables, counter=None, del_overlap=True):

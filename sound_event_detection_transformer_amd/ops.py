@@ -1784,6 +1784,33 @@ def pseudo_labels(logits, boxes, at, thr, min_len, tables, counter=None, del_ove
                                         _p(counter), cap, L.stream_ptr()), 'pseudo_labels')
 
 
+def event_metrics_update(scores, labels, boxes, at_tags, clip_idx, table, n_clips, max_ref, ev_counts, tag_counts, fusion,
+                         threshold=0.5, min_duration=0.2, max_len=10.0, t_collar=0.2, pct=0.2, del_overlap=True, optimal=True):
+    """decode_strong + sed_eval's event-based and clip-level counts of one fusion strategy's PostProcess outputs, accumulated into
+    ev_counts int64 [n_fusion, C, 3] / tag_counts int64 [n_fusion + 1, C, 3] (include/sedt_hip.h: sedt_event_metrics_update).
+    table: dict of the device reference table (present int32 [n_clips], off int32 [n_clips + 1], cls int32, on / end float64);
+    clip_idx int32 [B] (-1 = outside the table); at_tags int64 [B, C] or None."""
+    _dev_check(scores, labels, boxes, clip_idx, ev_counts, tag_counts)
+    B, Q = scores.shape
+    nf, C = ev_counts.shape[0], ev_counts.shape[1]
+    assert scores.dtype == torch.float32 and labels.dtype == torch.int64 and boxes.dtype == torch.float32
+    assert scores.is_contiguous() and labels.is_contiguous() and boxes.is_contiguous() and tuple(boxes.shape) == (B, Q, 2)
+    assert tuple(labels.shape) == (B, Q) and clip_idx.dtype == torch.int32 and clip_idx.numel() == B and clip_idx.is_contiguous()
+    assert ev_counts.dtype == torch.int64 and tuple(ev_counts.shape) == (nf, C, 3) and ev_counts.is_contiguous()
+    assert tag_counts.dtype == torch.int64 and tuple(tag_counts.shape) == (nf + 1, C, 3) and tag_counts.is_contiguous()
+    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_clips + 1
+    assert table['present'].dtype == torch.int32 and table['present'].numel() >= n_clips
+    assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
+    if at_tags is not None:
+        assert at_tags.dtype == torch.int64 and tuple(at_tags.shape) == (B, C) and at_tags.is_contiguous() and at_tags.is_cuda
+    L.check(L.load().sedt_event_metrics_update(_p(scores), _p(labels), _p(boxes), _p(at_tags), _p(clip_idx), _p(table['present']),
+                                               _p(table['off']),
+                                               _p(table['cls']), _p(table['on']), _p(table['end']), int(n_clips), int(max_ref), B, Q, C,
+                                               nf, int(fusion), float(threshold), float(min_duration), float(max_len), float(t_collar),
+                                               float(pct), int(bool(del_overlap)), int(bool(optimal)), _p(ev_counts), _p(tag_counts),
+                                               L.stream_ptr()), 'event_metrics_update')
+
+
 def mixup(x1, x2, jobs, out=None):
     """feature half of utilities/mixup.py: out[i] = lam * x1[src1] + (1 - lam) * x2[src2] / x1[src1] / x2[src2] per job record
     (jobs: uint8 device tensor of n 16-byte records {int32 src1, src2, mode; f32 lam}); x1 / x2 / out f32 [*, clip...]"""
