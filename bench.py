@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: SEDT training throughput (audio clips/s) on synthetic batches, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dtype bf16|f32] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dtype bf16|f32] [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher: this script starts N ranks ITSELF (``python -m torch.distributed.run`` as a child process,
 before the parent touches the GPU) and relays rank 0's JSON line.  Under a launcher (WORLD_SIZE set) it is one rank;
@@ -13,9 +13,12 @@ A step = one full training step of the chosen BASELINE.json configuration, as HI
   c3: DCASE SEDT E=6 Q=20, B=32 = 16 strong + 16 weak clips
   c4: SP-SEDT pre-training E=6 Q=20, 10 patches per clip, B=200/GPU, backbone frozen, feature-reconstruction loss
   c5: mean-teacher step E=6 Q=20: 32 labelled (16+16) + 32 unlabelled clips through teacher (no grad) and student
-Prints ONE JSON line (rank 0): clips/s over all ranks, `roofline` (whole-step MFMA roofline from HIP events on the launch
-stream + the GEMM family replayed alone + PMC traffic from profiles/), `kernels` (per-kernel MFMA utilisation / HBM GB/s
-for the north-star kernels, timed live with HIP events), `cpu_baseline` (the CPU oracle on this box's host cores).
+Prints ONE JSON line (rank 0): clips/s over all ranks and `roofline` (whole-step MFMA roofline from HIP events on the launch
+stream + PMC traffic from profiles/).  A plain run does nothing else: set-up, settle, warm-up, the timed steps, --dump-outputs.
+--full adds, after the timed region, what takes runs of its own: `roofline.gemm_family` (the GEMM family replayed alone) and
+`roofline.families` (per-kernel rooflines), `kernels` (per-kernel MFMA utilisation / HBM GB/s for the north-star kernels, timed
+live with HIP events), `other_configs`, `cpu_baseline` (the CPU oracle on this box's host cores), `clocks_under_load`,
+`host_launch_us_per_step` and, at N > 1, `exposed_comm`; the --no-* switches drop single legs of it.
 """
 import argparse
 import json
@@ -51,6 +54,10 @@ def parse():
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32', 'bf16x3'],
                     help="bf16 = throughput mode (BASELINE configs[1]); f32 = exact-f32 parity mode; bf16x3 = parity-grade fast mode (f32 tensors, "
                          "split-bf16 products: meets the 1e-3 tolerance)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run what the headline figure does not need: GEMM family and per-kernel rooflines, '
+                         'the per-kernel report, the other configurations and precisions, the CPU baseline, clocks under load, host '
+                         'issue time, exposed communication (the --no-* switches below drop single legs of it)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernels', action='store_true', help='skip the per-kernel report')
     ap.add_argument('--dump-igemm', default=None, help='write per-launch igemm timings (json) to this path')
@@ -1173,17 +1180,19 @@ def main():
     last = None
     # the host's own cost of ISSUING a step (table refresh, graph launches, RCCL enqueues): three steps queued onto an idle device - the
     # pinned upload rings have four slots, so the host does not block on the GPU inside this burst.  Every rank runs it (collectives match)
-    t1 = time.perf_counter()
-    for _ in range(3):
-        step()
-    host_issue = (time.perf_counter() - t1) / 3.0
-    barrier()
+    host_issue = None
+    if args.full:
+        t1 = time.perf_counter()
+        for _ in range(3):
+            step()
+        host_issue = (time.perf_counter() - t1) / 3.0
+        barrier()
     dev_ms = e0.elapsed_time(e1) / args.steps           # HIP events on the stream the step's graphs are launched on
     per_rank = [elapsed]
     rccl_world = 1
     # clocks UNDER LOAD, after the timed region: rocm-smi runs in a child while this process keeps replaying the step
     clocks = None
-    if rank == 0 and world == 1 and graphed and not args.no_clocks:      # (world > 1: a step contains collectives - no rank may run extra ones)
+    if args.full and rank == 0 and world == 1 and graphed and not args.no_clocks:   # (world > 1: a step contains collectives - no rank may run extra ones)
         clocks = clocks_under_load(step)
     if world > 1:
         dist = torch.distributed
@@ -1196,7 +1205,7 @@ def main():
 
     # ---- exposed communication: the same step without the data-parallel schedule (local gradients only), same process
     exposed = None
-    if world > 1 and graphed and 'local_step' in ex:
+    if args.full and world > 1 and graphed and 'local_step' in ex:
         try:                                   # a diagnostic after the timed region: never allowed to cost the result line
             loc = ex['local_step']()
             for _ in range(3):
@@ -1220,7 +1229,7 @@ def main():
     #      then replayed back to back on the launch stream between two HIP events
     gemm = None
     gemm_rec = None
-    if args.config in ('c2', 'c3') and not args.model_only and not args.no_gemm_family:
+    if args.full and args.config in ('c2', 'c3') and not args.model_only and not args.no_gemm_family:
         if rank != 0 and world > 1 and not graphed:
             ops.PROFILE = []                      # eager DDP: the extra step contains collectives, every rank must take part
             from sound_event_detection_transformer_amd.engine import train_step
@@ -1282,7 +1291,7 @@ def main():
     # ---- per-kernel-family roofline of the measured step (rank 0): in-process kernel trace of three further steps, joined with the
     #      shapes of the recorded GEMM launches
     fam = None
-    if rank == 0 and world == 1 and graphed and not args.no_families and not args.model_only:
+    if args.full and rank == 0 and world == 1 and graphed and not args.no_families and not args.model_only:
         try:
             n_params = sum(p.numel() for p in ex['model'].parameters() if p.requires_grad)
             fam = family_report(step, gemm_rec, args.dtype, n_params, dev_ms)
@@ -1305,7 +1314,7 @@ def main():
         roof = {"bound": "mfma",
                 "kernel": "whole training-step graph (>= 99 % of its algorithmic flops are the MFMA implicit-GEMM family "
                           "sedt::igemm3* / wgrad3/4*)" + (f"; dominant kernel by time: {dom['kernel']} - see dominant / families" if dom else
-                                                          "; see gemm_family and kernels"),
+                                                          "; see gemm_family and kernels" if args.full else "; per-kernel figures: --full"),
                 "achieved": round(ach / 1e12, 2), "peak": peak / 1e12, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
                 "traffic": None if traffic is None else traffic.get('hbm_bytes_per_step'),
                 "traffic_source": traffic_why if traffic is None else traffic.get('source'),
@@ -1318,15 +1327,15 @@ def main():
             if roof.get("traffic") and fam.get("algorithmic_bytes"):
                 roof["traffic_over_algorithmic"] = round(roof["traffic"] / fam["algorithmic_bytes"], 2)
         kernels = None
-        if not args.no_kernels and args.config == 'c2':
+        if args.full and not args.no_kernels and args.config == 'c2':
             try:
                 kernels = kernel_report(args.dtype, dev)
             except Exception as e:                                   # the report must never cost the headline number
                 kernels = [{"error": repr(e)}]
         others = None
-        if args.config == 'c2' and world == 1 and graphed and not args.no_other_configs and args.dtype == 'bf16' and not args.batch:
+        if args.full and args.config == 'c2' and world == 1 and graphed and not args.no_other_configs and args.dtype == 'bf16' and not args.batch:
             others = other_configs(args, dev, (ex, step))
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline()
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline()
         value = world * clips * args.steps / elapsed
         kind = "inference (validation step)" if args.config == 'eval' else "training"
         out = {"metric": f"audio clips/sec {kind} throughput (B={clips}, 10s@64-mel)", "value": round(value, 2),
@@ -1342,7 +1351,7 @@ def main():
                "clocks_under_load": clocks,
                # time the host spends ISSUING one step (table refresh, graph launches, RCCL enqueues; measured as a burst of three onto an idle device): while
                # this stays below ms_per_step the GPU never waits for the host; at N > 1 it tells exposed communication from host issue time
-               "host_launch_us_per_step": round(host_issue * 1e6, 1)}
+               "host_launch_us_per_step": None if host_issue is None else round(host_issue * 1e6, 1)}
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if others is not None:

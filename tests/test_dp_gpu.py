@@ -321,13 +321,14 @@ def test_eager_step_under_torch_ddp_matches_plain_eager_step(tmp_path):
 
 def _run_bench_world2(extra, transport=('--backend', 'gloo', '--share-gpu')):
     """bench.py's own rank path, launched exactly as the driver launches it (python -m torch.distributed.run, one process per rank),
-    two ranks sharing the one test GPU over gloo - or, transport=('--backend', 'nccl'), one GPU per rank over RCCL"""
+    two ranks sharing the one test GPU over gloo - or, transport=('--backend', 'nccl'), one GPU per rank over RCCL.  --full: the tests read
+    `exposed_comm`, which only a full run measures"""
     import json
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--settle', '2',
-           '--batch', '4', *transport, '--no-cpu-baseline', '--no-kernels', '--no-other-configs'] + extra
+           '--batch', '4', *transport, '--full', '--no-cpu-baseline', '--no-kernels', '--no-other-configs'] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{') and '"metric"' in l]

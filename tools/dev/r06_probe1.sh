@@ -13,7 +13,7 @@ rocprofv3 --pmc TCC_REQ_sum TCC_READ_sum --kernel-trace --output-format csv -d $
 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_BUBBLE_sum --kernel-trace --output-format csv -d $out/pmc_dram -- $B --config c2 > $out/pmc_dram.log 2>&1 || echo "pmc dram failed"
 python3 $root/tools/pmc_cache_summary.py $out/cache_c2.csv $out/pmc_hit $out/pmc_rd $out/pmc_req $out/pmc_dram > $out/cache_c2.log 2>&1
 for c in c3 c4 c5; do
-  rocprofv3 --kernel-trace --output-format csv -d $out/trace_$c -- python3 $root/bench.py --config $c --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families > $out/trace_$c.log 2>&1 || echo "trace $c failed"
+  rocprofv3 --kernel-trace --output-format csv -d $out/trace_$c -- python3 $root/bench.py --full --config $c --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families > $out/trace_$c.log 2>&1 || echo "trace $c failed"
   python3 $root/tools/step_sequence.py $out/trace_$c $out/step_sequence_$c.txt $([ $c = c3 ] && echo 1 || echo 2) > $out/seq_$c.log 2>&1
 done
 # keep the merge small: drop the raw traces / counter dumps, keep summaries

@@ -11,7 +11,7 @@ python tools/glue_ops.py c4 aten > $out/glue_c4.txt 2>&1
 python tools/glue_ops.py c5 aten > $out/glue_c5.txt 2>&1
 python tools/glue_ops.py c3 aten > $out/glue_c3.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $out/trace_x3 -- python3 $root/bench.py --config c2 --dtype bf16x3 --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families --no-clocks --model-only-off 2> /dev/null > $out/trace_x3.log || rocprofv3 --kernel-trace --output-format csv -d $out/trace_x3 -- python3 $root/bench.py --config c2 --dtype bf16x3 --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families --no-clocks > $out/trace_x3.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $out/trace_x3 -- python3 $root/bench.py --full --config c2 --dtype bf16x3 --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families --no-clocks --model-only-off 2> /dev/null > $out/trace_x3.log || rocprofv3 --kernel-trace --output-format csv -d $out/trace_x3 -- python3 $root/bench.py --full --config c2 --dtype bf16x3 --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families --no-clocks > $out/trace_x3.log 2>&1
 python3 $root/tools/step_sequence.py $out/trace_x3 $out/step_sequence_x3.txt > $out/seq_x3.log 2>&1
 rm -rf $out/trace_x3
 ls -la $out

@@ -8,7 +8,7 @@ bash tools/profile_round.sh r06 c2 c3 c4 c5 > gpurun_out/prof_r06.log 2>&1
 PMC_CFG=c4 bash tools/profile_round.sh r06c4 c4 > gpurun_out/prof_r06c4.log 2>&1
 PMC_CFG=c5 bash tools/profile_round.sh r06c5 c5 > gpurun_out/prof_r06c5.log 2>&1
 P=gpurun_out/prof_r06
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$P/trace_c2x3 -- python3 $root/bench.py --config c2 --dtype bf16x3 --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families --no-clocks --no-gemm-family > $root/$P/trace_c2x3.log 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$P/trace_c2x3 -- python3 $root/bench.py --full --config c2 --dtype bf16x3 --steps 5 --warmup 2 --settle 0 --no-cpu-baseline --no-kernels --no-other-configs --no-families --no-clocks --no-gemm-family > $root/$P/trace_c2x3.log 2>&1 )
 S=gpurun_out/r06_summaries
 mkdir -p $S
 python3 tools/pmc_step_summary.py $P $S/r06_step_c2.csv $S/r06_pmc_c2.json c2 1 > $S/sum_c2.log 2>&1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The ordered kernel sequence of ONE steady-state step from a rocprofv3 kernel trace of bench.py: index, start offset, duration,
+"""The ordered kernel sequence of ONE steady-state step from a rocprofv3 kernel trace of `bench.py --full`: index, start offset, duration,
 gap to the previous kernel's end, name.  Steps are split at the stem forward kernel.
 usage: step_sequence.py <dir with *_kernel_trace.csv> [out.txt] [stem launches per step, default 1: C4 (clips + patches) and C5 (teacher +
 student) run the stem twice per step]"""
@@ -14,7 +14,7 @@ rows = list(csv.DictReader(open(f)))
 ev = sorted((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name']) for r in rows)
 idx = [i for i, e in enumerate(ev) if 'stem_pool_fwd' in e[2] or 'stem_im2col' in e[2]]
 per = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-# a step INSIDE bench.py's timed loop: the last three replays of a run are the host-issue burst that follows the closing barrier (round 6)
+# a step INSIDE bench.py's timed loop: the last three replays of a --full run are the host-issue burst that follows the closing barrier
 a, b = idx[-6 * per], idx[-5 * per]
 seg = ev[a:b]
 
