@@ -30,6 +30,7 @@
  *   sedt_event_metrics_update                                                 decode_strong + sed_eval event-based / clip-level counts
  *                                                                             utilities/BoxEncoder.py:179-226, engine.py:199-297,
  *                                                                             utilities/metrics.py:43-80, 281-322
+ *   sedt_event_segment_metrics_update                                         + sed_eval segment-based counts  utilities/metrics.py:83-116
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -758,6 +759,22 @@ int sedt_event_metrics_update(const float* scores, const int64_t* labels, const 
                               const double* ref_end, int n_clips, int max_ref, int B, int Q, int C, int n_fusion, int fusion,
                               float threshold, float min_duration, double max_len, double t_collar, double pct, int del_overlap,
                               int optimal, int64_t* ev_counts, int64_t* tag_counts, void* stream);
+/* sedt_event_segment_metrics_update (utilities/metrics.py:83-116, 147-157: sed_eval SegmentBasedMetrics): the same launch, the same
+ * arguments and the same ev / tag counts, plus the segment-based counts of the clips in the reference at resolution time_resolution
+ * (seconds, > 0).  After the decode and the hit graph, the survivors (clipped to [0, max_len], in float64) and the clip's reference
+ * events are rasterised into per-class bit rows in LDS: event (c, on, off) sets segments floor(on / r) <= k < ceil(off / r), both
+ * quotients float64 divisions (sed_eval's event roll), over n_seg_words words of 64 segments (1 .. 16: at most 1024 segments; the
+ * host bounds ceil(max(max_len, largest reference offset) / r) by n_seg_words * 64 and keeps reference times >= 0).
+ *   seg_counts [n_fusion][C][3] += {tp, n_ref, n_sys}: class-wise segments active in both / in the reference / in the estimates;
+ *   sdi_counts [n_fusion][3]    += {S, D, I}: per segment over the classes, S = min(Nref, Nsys) - Ntp, D = max(0, Nref - Nsys),
+ *   I = max(0, Nsys - Nref).  Integer atomics only. */
+int sedt_event_segment_metrics_update(const float* scores, const int64_t* labels, const float* boxes, const int64_t* at_tags,
+                                      const int32_t* clip_idx, const int32_t* ref_present, const int32_t* ref_off,
+                                      const int32_t* ref_cls, const double* ref_on, const double* ref_end, int n_clips, int max_ref,
+                                      int B, int Q, int C, int n_fusion, int fusion, float threshold, float min_duration,
+                                      double max_len, double t_collar, double pct, int del_overlap, int optimal, int64_t* ev_counts,
+                                      int64_t* tag_counts, double time_resolution, int n_seg_words, int64_t* seg_counts,
+                                      int64_t* sdi_counts, void* stream);
 
 /* ------------------------------------------------------------------ input side on the device (utilities/BoxTransforms.py,
  * utilities/mixup.py)

@@ -2,9 +2,12 @@
 //   * event_metrics_kernel   BoxEncoder.decode_strong (utilities/BoxEncoder.py:179-226) + the clip to [0, max_len] (engine.py:287)
 //                            + sed_eval EventBasedMetrics counts (metrics.py:43-80: t_collar, percentage_of_length, onset and offset)
 //                            + clip-level tag counts of the decoded events and of the audio-tag head (metrics.py:281-322)
+//                            + (SEG) sed_eval SegmentBasedMetrics counts (metrics.py:83-116): class-wise and per-segment S / D / I
 // One wave per clip.  The decode runs in f32 on PostProcess's f32 values, exactly as the reference's numpy / torch scalars do; the
 // matching conditions run in float64 on those values, as sed_eval compares Python floats.  Counts land in int64 counters through
 // integer atomics only: every result is independent of the order the clips arrive in.
+#include <cfloat>
+
 #include "common.h"
 
 #pragma clang fp contract(off)     // the float64 collar tests must be the plain sub / mul / compare sed_eval evaluates
@@ -14,11 +17,30 @@ namespace sedt {
 #define SEDT_EM_MAXQ 64            // queries per clip (one lane each)
 #define SEDT_EM_MAXC 63            // classes (one lane each in the per-class passes)
 #define SEDT_EM_MAXR 64            // reference events per clip (one bit row of the hit graph each)
+#define SEDT_EM_MAXSEG 1024        // segments per clip of the segment-based counts (10 s at 10 ms)
+#define SEDT_EM_SEGW (SEDT_EM_MAXSEG / 64)   // 64-bit words of one class's segment row
+
+// segments floor(on / r) <= k < ceil(off / r) of one event into its class's bit row (W words): float64 divisions, as sed_eval's
+// event_list_to_event_roll computes `onset * 1 / time_resolution`; an empty range sets nothing, events of one class OR together
+__device__ inline void seg_raster(unsigned long long* row, double on, double off, double r, int W) {
+  const double nb = 64.0 * W;       // the host bounds every ceil(off / r) by the roll length: the clamps only keep LDS in range
+  const int k0 = (int)fmin(fmax(floor(on / r), 0.0), nb), k1 = (int)fmin(fmax(ceil(off / r), 0.0), nb);
+  if (k0 >= k1) return;
+  for (int w = k0 >> 6; 64 * w < k1; ++w) {
+    const int lo = max(k0 - 64 * w, 0), hi = min(k1 - 64 * w, 64);
+    const unsigned long long m = (hi == 64 ? ~0ull : (1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);
+    atomicOr(row + w, m);                                           // ds_or_b64
+  }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // block = 64 threads = one wave, blockIdx.x = clip of the batch.
 //   ev  [n_fusion][C][3] += {tp, n_ref, n_sys}       (only clips that are in the reference: clip_idx >= 0)
 //   tag [n_fusion + 1][C][3] += {tp, fp, fn}         (every clip: reference clips and clips without any reference row alike)
+// SEG: the segment-based counts at resolution seg_res over seg_words words of 64 segments (reference clips only):
+//   seg [n_fusion][C][3] += {tp, n_ref, n_sys}       (segments where the class is active in both / in the reference / in the estimates)
+//   sdi [n_fusion][3]    += {S, D, I}                (per segment over the classes: substitutions, deletions, insertions)
+template <bool SEG>
 __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restrict__ scores, const int64_t* __restrict__ labels,
                                                            const float* __restrict__ boxes, const int64_t* __restrict__ at_tags,
                                                            const int32_t* __restrict__ clip_idx, const int32_t* __restrict__ ref_present,
@@ -27,7 +49,8 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
                                                            const double* __restrict__ ref_end, int n_clips, int Q, int C, int n_fusion,
                                                            int fusion, float threshold, float min_dur, double max_len, double t_collar,
                                                            double pct, int del_overlap, int optimal, unsigned long long* __restrict__ ev,
-                                                           unsigned long long* __restrict__ tag) {
+                                                           unsigned long long* __restrict__ tag, double seg_res, int seg_words,
+                                                           unsigned long long* __restrict__ seg, unsigned long long* __restrict__ sdi) {
   __shared__ float s_on[SEDT_EM_MAXQ], s_end[SEDT_EM_MAXQ], s_score[SEDT_EM_MAXQ];
   __shared__ int s_lab[SEDT_EM_MAXQ], s_keep[SEDT_EM_MAXQ], s_surv[SEDT_EM_MAXQ], s_order[SEDT_EM_MAXQ];
   __shared__ int r_cls[SEDT_EM_MAXR];
@@ -186,6 +209,88 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
       if (ref_has && !at_has) atomicAdd(a + 2, 1ull);
     }
   }
+
+  // ---- segment-based counts (sed_eval SegmentBasedMetrics): the clipped survivors (the values the hit test used) and the clip's
+  // reference events as per-class bit rows, roll_*[c * W + w] bit b = segment 64 w + b; the roll lengths and their padding only add
+  // true negatives, which are not counted
+  if constexpr (SEG) {
+    if (clip < 0) return;                                          // block-uniform: only reference clips are evaluated
+    __shared__ unsigned long long roll_ref[SEDT_EM_MAXC * SEDT_EM_SEGW], roll_sys[SEDT_EM_MAXC * SEDT_EM_SEGW];
+    const int W = seg_words;
+    for (int i = lane; i < C * W; i += 64) {
+      roll_ref[i] = 0ull;
+      roll_sys[i] = 0ull;
+    }
+    __syncthreads();
+    if (surv) seg_raster(roll_sys + lab * W, my_on, my_end, seg_res, W);
+    if (lane < ne) seg_raster(roll_ref + r_cls[lane] * W, r_on[lane], r_end[lane], seg_res, W);
+    __syncthreads();
+    // class-wise (lane = class): segments active in both, in the reference, in the estimates
+    int s_tp = 0, s_ref = 0, s_sys = 0;
+    if (c < C) {
+      for (int w = 0; w < W; ++w) {
+        const unsigned long long a = roll_ref[c * W + w], s = roll_sys[c * W + w];
+        s_tp += __popcll(a & s);
+        s_ref += __popcll(a);
+        s_sys += __popcll(s);
+      }
+      unsigned long long* e = seg + ((long)fusion * C + c) * 3;
+      if (s_tp) atomicAdd(e, (unsigned long long)s_tp);
+      if (s_ref) atomicAdd(e + 1, (unsigned long long)s_ref);
+      if (s_sys) atomicAdd(e + 2, (unsigned long long)s_sys);
+    }
+    // per segment (lane = bit of the word), over the classes active anywhere in the clip (the others add nothing):
+    // S += min(Nref, Nsys) - Ntp, D += max(0, Nref - Nsys), I += max(0, Nsys - Nref)
+    const unsigned long long act = __ballot(c < C && (s_ref | s_sys) != 0);
+    int n_sub = 0, n_del = 0, n_ins = 0;
+    for (int w = 0; w < W; ++w) {
+      int nref = 0, nsys = 0, ntp = 0;
+      for (unsigned long long m = act; m; m &= m - 1ull) {
+        const int k = (__ffsll((long long)m) - 1) * W + w;
+        const int a = (int)(roll_ref[k] >> lane) & 1, s = (int)(roll_sys[k] >> lane) & 1;
+        nref += a;
+        nsys += s;
+        ntp += a & s;
+      }
+      n_sub += min(nref, nsys) - ntp;
+      n_del += max(0, nref - nsys);
+      n_ins += max(0, nsys - nref);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      n_sub += __shfl_xor(n_sub, o, 64);
+      n_del += __shfl_xor(n_del, o, 64);
+      n_ins += __shfl_xor(n_ins, o, 64);
+    }
+    if (lane == 0) {
+      unsigned long long* t = sdi + (long)fusion * 3;
+      if (n_sub) atomicAdd(t, (unsigned long long)n_sub);
+      if (n_del) atomicAdd(t + 1, (unsigned long long)n_del);
+      if (n_ins) atomicAdd(t + 2, (unsigned long long)n_ins);
+    }
+  }
+}
+
+template <bool SEG>
+int event_metrics_launch(const char* what, const float* scores, const int64_t* labels, const float* boxes, const int64_t* at_tags,
+                         const int32_t* clip_idx, const int32_t* ref_present, const int32_t* ref_off, const int32_t* ref_cls,
+                         const double* ref_on, const double* ref_end, int n_clips, int max_ref, int B, int Q, int C, int n_fusion,
+                         int fusion, float threshold, float min_duration, double max_len, double t_collar, double pct, int del_overlap,
+                         int optimal, int64_t* ev_counts, int64_t* tag_counts, double seg_res, int seg_words, int64_t* seg_counts,
+                         int64_t* sdi_counts, void* stream) {
+  SEDT_REQUIRE(scores && labels && boxes && clip_idx && ref_off && ev_counts && tag_counts, "event_metrics_update: null pointer");
+  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_EM_MAXQ && C >= 1 && C <= SEDT_EM_MAXC, "event_metrics_update: B=%d Q=%d (<=%d) C=%d (<=%d)",
+               B, Q, SEDT_EM_MAXQ, C, SEDT_EM_MAXC);
+  SEDT_REQUIRE(n_clips >= 0 && (n_clips == 0 || (ref_cls && ref_on && ref_end)), "event_metrics_update: reference table missing");
+  SEDT_REQUIRE(max_ref >= 0 && max_ref <= SEDT_EM_MAXR, "event_metrics_update: a clip has %d reference events (<= %d)", max_ref,
+               SEDT_EM_MAXR);
+  SEDT_REQUIRE(n_fusion >= 1 && fusion >= 0 && fusion < n_fusion, "event_metrics_update: fusion %d of %d", fusion, n_fusion);
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(event_metrics_kernel<SEG>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), scores, labels, boxes,
+                     at_tags, clip_idx, ref_present, ref_off, ref_cls, ref_on, ref_end, n_clips, Q, C, n_fusion, fusion, threshold,
+                     min_duration, max_len, t_collar, pct, del_overlap, optimal, reinterpret_cast<unsigned long long*>(ev_counts),
+                     reinterpret_cast<unsigned long long*>(tag_counts), seg_res, seg_words,
+                     reinterpret_cast<unsigned long long*>(seg_counts), reinterpret_cast<unsigned long long*>(sdi_counts));
+  return check_launch(what);
 }
 
 }  // namespace sedt
@@ -196,18 +301,27 @@ extern "C" int sedt_event_metrics_update(const float* scores, const int64_t* lab
                                          const double* ref_end, int n_clips, int max_ref, int B, int Q, int C, int n_fusion, int fusion,
                                          float threshold, float min_duration, double max_len, double t_collar, double pct,
                                          int del_overlap, int optimal, int64_t* ev_counts, int64_t* tag_counts, void* stream) {
+  return sedt::event_metrics_launch<false>("event_metrics_update", scores, labels, boxes, at_tags, clip_idx, ref_present, ref_off,
+                                           ref_cls, ref_on, ref_end, n_clips, max_ref, B, Q, C, n_fusion, fusion, threshold,
+                                           min_duration, max_len, t_collar, pct, del_overlap, optimal, ev_counts, tag_counts, 0.0, 0,
+                                           nullptr, nullptr, stream);
+}
+
+extern "C" int sedt_event_segment_metrics_update(const float* scores, const int64_t* labels, const float* boxes, const int64_t* at_tags,
+                                                 const int32_t* clip_idx, const int32_t* ref_present, const int32_t* ref_off,
+                                                 const int32_t* ref_cls, const double* ref_on, const double* ref_end, int n_clips,
+                                                 int max_ref, int B, int Q, int C, int n_fusion, int fusion, float threshold,
+                                                 float min_duration, double max_len, double t_collar, double pct, int del_overlap,
+                                                 int optimal, int64_t* ev_counts, int64_t* tag_counts, double time_resolution,
+                                                 int n_seg_words, int64_t* seg_counts, int64_t* sdi_counts, void* stream) {
   using namespace sedt;
-  SEDT_REQUIRE(scores && labels && boxes && clip_idx && ref_off && ev_counts && tag_counts, "event_metrics_update: null pointer");
-  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_EM_MAXQ && C >= 1 && C <= SEDT_EM_MAXC, "event_metrics_update: B=%d Q=%d (<=%d) C=%d (<=%d)",
-               B, Q, SEDT_EM_MAXQ, C, SEDT_EM_MAXC);
-  SEDT_REQUIRE(n_clips >= 0 && (n_clips == 0 || (ref_cls && ref_on && ref_end)), "event_metrics_update: reference table missing");
-  SEDT_REQUIRE(max_ref >= 0 && max_ref <= SEDT_EM_MAXR, "event_metrics_update: a clip has %d reference events (<= %d)", max_ref,
-               SEDT_EM_MAXR);
-  SEDT_REQUIRE(n_fusion >= 1 && fusion >= 0 && fusion < n_fusion, "event_metrics_update: fusion %d of %d", fusion, n_fusion);
-  if (B == 0) return 0;
-  hipLaunchKernelGGL(event_metrics_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), scores, labels, boxes, at_tags,
-                     clip_idx, ref_present, ref_off, ref_cls, ref_on, ref_end, n_clips, Q, C, n_fusion, fusion, threshold, min_duration, max_len,
-                     t_collar, pct, del_overlap, optimal, reinterpret_cast<unsigned long long*>(ev_counts),
-                     reinterpret_cast<unsigned long long*>(tag_counts));
-  return check_launch("event_metrics_update");
+  SEDT_REQUIRE(seg_counts && sdi_counts, "event_segment_metrics_update: null pointer");
+  SEDT_REQUIRE(time_resolution > 0.0 && time_resolution <= DBL_MAX, "event_segment_metrics_update: time_resolution %g", time_resolution);
+  SEDT_REQUIRE(n_seg_words >= 1 && n_seg_words <= SEDT_EM_SEGW,
+               "event_segment_metrics_update: %d segment words (1 .. %d: at most %d segments per clip)", n_seg_words, SEDT_EM_SEGW,
+               SEDT_EM_MAXSEG);
+  return event_metrics_launch<true>("event_segment_metrics_update", scores, labels, boxes, at_tags, clip_idx, ref_present, ref_off,
+                                    ref_cls, ref_on, ref_end, n_clips, max_ref, B, Q, C, n_fusion, fusion, threshold, min_duration,
+                                    max_len, t_collar, pct, del_overlap, optimal, ev_counts, tag_counts, time_resolution, n_seg_words,
+                                    seg_counts, sdi_counts, stream);
 }

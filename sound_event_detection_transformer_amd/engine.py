@@ -708,7 +708,7 @@ class GraphedPredictStep(object):
                 raise RuntimeError('GraphedPredictStep(metrics=...): call metrics.set_reference() before building the step')
             self.clip_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.metrics_gen = metrics.generation
-            saved = (metrics.ev.clone(), metrics.tag.clone())          # the warm-up runs count too: put the counters back after
+            saved = [t.clone() for t in metrics.counters()]            # the warm-up runs count too: put the counters back after
         stream = train_stream(dev)
         stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(stream):
@@ -717,8 +717,8 @@ class GraphedPredictStep(object):
         torch.cuda.current_stream().wait_stream(stream)
         torch.cuda.synchronize()
         if metrics is not None:
-            metrics.ev.copy_(saved[0])
-            metrics.tag.copy_(saved[1])
+            for t, s in zip(metrics.counters(), saved):
+                t.copy_(s)
             torch.cuda.synchronize()
         quiesce_collectives(dev)
         self.graph = torch.cuda.CUDAGraph()

@@ -1785,11 +1785,14 @@ def pseudo_labels(logits, boxes, at, thr, min_len, tables, counter=None, del_ove
 
 
 def event_metrics_update(scores, labels, boxes, at_tags, clip_idx, table, n_clips, max_ref, ev_counts, tag_counts, fusion,
-                         threshold=0.5, min_duration=0.2, max_len=10.0, t_collar=0.2, pct=0.2, del_overlap=True, optimal=True):
+                         threshold=0.5, min_duration=0.2, max_len=10.0, t_collar=0.2, pct=0.2, del_overlap=True, optimal=True,
+                         seg_counts=None, sdi_counts=None, time_resolution=1.0, n_seg_words=1):
     """decode_strong + sed_eval's event-based and clip-level counts of one fusion strategy's PostProcess outputs, accumulated into
     ev_counts int64 [n_fusion, C, 3] / tag_counts int64 [n_fusion + 1, C, 3] (include/sedt_hip.h: sedt_event_metrics_update).
     table: dict of the device reference table (present int32 [n_clips], off int32 [n_clips + 1], cls int32, on / end float64);
-    clip_idx int32 [B] (-1 = outside the table); at_tags int64 [B, C] or None."""
+    clip_idx int32 [B] (-1 = outside the table); at_tags int64 [B, C] or None.  With seg_counts int64 [n_fusion, C, 3] and
+    sdi_counts int64 [n_fusion, 3] the same launch adds sed_eval's segment-based counts at ``time_resolution`` seconds over
+    ``n_seg_words`` words of 64 segments per clip (sedt_event_segment_metrics_update)."""
     _dev_check(scores, labels, boxes, clip_idx, ev_counts, tag_counts)
     B, Q = scores.shape
     nf, C = ev_counts.shape[0], ev_counts.shape[1]
@@ -1803,12 +1806,22 @@ def event_metrics_update(scores, labels, boxes, at_tags, clip_idx, table, n_clip
     assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
     if at_tags is not None:
         assert at_tags.dtype == torch.int64 and tuple(at_tags.shape) == (B, C) and at_tags.is_contiguous() and at_tags.is_cuda
-    L.check(L.load().sedt_event_metrics_update(_p(scores), _p(labels), _p(boxes), _p(at_tags), _p(clip_idx), _p(table['present']),
-                                               _p(table['off']),
-                                               _p(table['cls']), _p(table['on']), _p(table['end']), int(n_clips), int(max_ref), B, Q, C,
-                                               nf, int(fusion), float(threshold), float(min_duration), float(max_len), float(t_collar),
-                                               float(pct), int(bool(del_overlap)), int(bool(optimal)), _p(ev_counts), _p(tag_counts),
-                                               L.stream_ptr()), 'event_metrics_update')
+    if seg_counts is None:
+        L.check(L.load().sedt_event_metrics_update(_p(scores), _p(labels), _p(boxes), _p(at_tags), _p(clip_idx), _p(table['present']),
+                                                   _p(table['off']),
+                                                   _p(table['cls']), _p(table['on']), _p(table['end']), int(n_clips), int(max_ref), B, Q, C,
+                                                   nf, int(fusion), float(threshold), float(min_duration), float(max_len), float(t_collar),
+                                                   float(pct), int(bool(del_overlap)), int(bool(optimal)), _p(ev_counts), _p(tag_counts),
+                                                   L.stream_ptr()), 'event_metrics_update')
+        return
+    _dev_check(seg_counts, sdi_counts)
+    assert seg_counts.dtype == torch.int64 and tuple(seg_counts.shape) == (nf, C, 3) and seg_counts.is_contiguous()
+    assert sdi_counts.dtype == torch.int64 and tuple(sdi_counts.shape) == (nf, 3) and sdi_counts.is_contiguous()
+    L.check(L.load().sedt_event_segment_metrics_update(
+        _p(scores), _p(labels), _p(boxes), _p(at_tags), _p(clip_idx), _p(table['present']), _p(table['off']), _p(table['cls']),
+        _p(table['on']), _p(table['end']), int(n_clips), int(max_ref), B, Q, C, nf, int(fusion), float(threshold), float(min_duration),
+        float(max_len), float(t_collar), float(pct), int(bool(del_overlap)), int(bool(optimal)), _p(ev_counts), _p(tag_counts),
+        float(time_resolution), int(n_seg_words), _p(seg_counts), _p(sdi_counts), L.stream_ptr()), 'event_segment_metrics_update')
 
 
 def mixup(x1, x2, jobs, out=None):
