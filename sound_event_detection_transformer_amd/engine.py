@@ -1,4 +1,6 @@
 """The per-batch body of the reference's ``engine.train`` loop (engine.py:56-80) as one function."""
+import contextlib
+import gc
 import math
 
 import os
@@ -93,6 +95,29 @@ def quiesce_collectives(dev=None):
         time.sleep(0.35)
 
 
+def _on_train_stream(dev, fn, *args, **kw):
+    """fn(*args, **kw) on the training stream of ``dev``, ordered after what the caller's stream holds and before what it
+    gets next (the eager steps use it when they are called on the default stream, see train_step)"""
+    side, cur = train_stream(dev), torch.cuda.current_stream(dev)
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        out = fn(*args, **kw)
+    cur.wait_stream(side)
+    return out
+
+
+def _warm_on_train_stream(dev, body, n):
+    """the warm-up runs of a stepper about to capture: n times ``body()`` on the training stream (the one the capture will use), the
+    device drained, the collectives of the runs retired (quiesce_collectives).  Nothing between this and the capture may start a
+    collective."""
+    def run():
+        for _ in range(n):
+            body()
+    _on_train_stream(dev, run)
+    torch.cuda.synchronize()
+    quiesce_collectives(dev)
+
+
 def train_step(model, criterion, optimizer, batch_input, targets, mask_weak=None, mask_strong=None, max_norm=0.1,
                normalize=False, check_finite=True, patches=None, allreduce=False, fine_tune=False, fl=False, mix_up_ratio=0,
                do_step=True):
@@ -112,13 +137,8 @@ def train_step(model, criterion, optimizer, batch_input, targets, mask_weak=None
         batch_input, (tuple, list)) else (batch_input[0] if len(batch_input) and torch.is_tensor(batch_input[0]) else None))
     dev = first.device if torch.is_tensor(first) else None
     if dev is not None and dev.type == 'cuda' and torch.cuda.current_stream(dev) == torch.cuda.default_stream(dev):
-        side, cur = train_stream(dev), torch.cuda.current_stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            out = train_step(model, criterion, optimizer, batch_input, targets, mask_weak, mask_strong, max_norm, normalize,
-                             check_finite, patches, allreduce, fine_tune, fl, mix_up_ratio, do_step)
-        cur.wait_stream(side)
-        return out
+        return _on_train_stream(dev, train_step, model, criterion, optimizer, batch_input, targets, mask_weak, mask_strong, max_norm,
+                                normalize, check_finite, patches, allreduce, fine_tune, fl, mix_up_ratio, do_step)
     if mix_up_ratio:
         from .utilities.mixup import mixup_data
         batch_input, targets, mask_strong, mask_weak = mixup_data(batch_input, targets, mask_strong, mask_weak, mix_up_ratio, alpha=1)
@@ -225,7 +245,8 @@ def dp_segment_plan(net, cuts='coarse'):
 
 class _GraphedBase(object):
     """what every graphed stepper shares: the optimizer's private chunk tables, the learning-rate refresh before each
-    replay, and the device-side non-finite-loss word (reference engine.py:70-73 / 167-169 abort on such a loss)."""
+    replay, the device-side non-finite-loss word (reference engine.py:70-73 / 167-169 abort on such a loss), and the
+    flat-gradient schedule - its set-up, the warm-up before a capture, the graphs captured after a stepper's first, their replay."""
     check_every = 50
 
     def _init_common(self, criterion, optimizer, dev):
@@ -308,7 +329,134 @@ class _GraphedBase(object):
             p.grad = g
         return self.optimizer.gather_grads(k, accumulate=accumulate)
 
+    # ---- the flat-gradient schedule: set-up, warm-up, capture of the graphs after the first, replay
+    def _setup_schedule(self, accum_steps, grad_dtype, data_parallel, ema_steps=None):
+        """world / dp / accum_steps / grad_dtype / flat_mode.  flat mode: gradients go through ONE flat buffer and the optimizer
+        (and the EMA update) is a graph of its own - data parallel: the all-reduce sits in between; accumulation: micro-batches add
+        into the buffer and only every accum_steps-th call runs the optimizer; ema_steps (the semi step): the EMA on its own period"""
+        dist = torch.distributed
+        grouped = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size() if grouped else 1
+        self.accum_steps, self.ema_steps, self._micro = int(accum_steps), int(1 if ema_steps is None else ema_steps), 0
+        if self.accum_steps < 1 or self.ema_steps < 1:
+            raise ValueError('accum_steps >= 1' if ema_steps is None else 'accum_steps / accumulating_ema_steps >= 1')
+        if self.accum_steps > 1 and grad_dtype == torch.bfloat16:
+            raise ValueError('accumulating micro-batch gradients in a bf16 flat buffer loses them: use the f32 buffer')
+        # data_parallel=True forces the data-parallel schedule (flat gradients, all-reduce, optimizer graph) even in a
+        # one-process group: lets a single GPU exercise the RCCL calls of the multi-GPU path
+        self.dp = (self.world > 1) if data_parallel is None else bool(data_parallel)
+        if self.dp and not grouped:
+            raise RuntimeError('data_parallel=True needs an initialised torch.distributed process group')
+        self.grad_dtype = grad_dtype
+        self.flat_mode = self.dp or self.accum_steps > 1 or self.ema_steps > 1
+        self.g_opt = self.g_ema = None
+        self.g_seg, self.flat_parts = [], []
+
+    def _sync_replicas(self, net, ema=None):
+        """replicas start identical (DDP does the same at wrap time), the teacher too - but drop different elements (seeds are
+        baked at capture)"""
+        if self.world < 2:
+            return
+        dist = torch.distributed
+        broadcast_parameters(net)
+        if ema is not None:
+            with torch.no_grad():
+                for n, p in net.named_parameters():
+                    if n in ema.shadow:
+                        h = ema.shadow[n] if dist.get_backend() == 'nccl' else ema.shadow[n].cpu()
+                        dist.broadcast(h, 0)
+                        ema.shadow[n].copy_(h)
+        self.runtime.seed_for_rank(dist.get_rank())
+
+    @contextlib.contextmanager
+    def _scope(self):
+        """what the warm-up bodies and every capture run under: this stepper's chunk tables and - where the body gives every
+        parameter ONE gradient contribution per backward (``defer`` of _warm_up) - the layers' weight gradients as one launch pair"""
+        with self.optimizer.table_set(self._tabname), ops.defer_layer_wgrads(enable=self._defer):
+            yield
+
+    def _warm_up(self, body, warmup, net, ema=None, defer=True):
+        """``warmup`` eager runs of ``body`` on the training stream (lazy initialisation of kernels, buffers, optimizer state), then
+        parameters, optimizer moments, step count, dropout counters (and EMA shadow) put back: the training state is the same before
+        and after.  Leaves self._capture (the arguments of every torch.cuda.graph of this stepper) and everything a capture must not
+        allocate.  defer: the body may hand the layers' weight gradients to ops.defer_layer_wgrads (see _scope)."""
+        opt = self.optimizer
+        self._defer = bool(defer)
+        self._capture = dict(stream=train_stream(self.dev), **_CAPTURE)
+        snap = _snapshot(net, opt, ema)
+        # gradients another stepper's captured backward left attached to the parameters would be ACCUMULATED into by the warm-up's
+        # eager backward (and the stack-level weight-gradient launches need fresh tensors: ops.defer_layer_wgrads)
+        opt.zero_grad(set_to_none=True)
+        with self._scope():
+            _warm_on_train_stream(self.dev, body, warmup)
+        # one order for both steppers: collectives quiesced (above, right after the last of them), flat buffer, collector.  Nothing
+        # from here to the capture starts a collective, so the watchdog gets nothing new to poll; the flat buffer exists since the
+        # first warm-up step's update (warmup=0: it is allocated here, still outside the capture), so the collector frees nothing it needs
+        _restore(net, opt, snap, ema)
+        self.nonfinite.zero_()
+        self.criterion.last_total = None      # drop the warm-up autograd graphs (their AccumulateGrad nodes belong to the stream)
+        opt.zero_grad(set_to_none=True)
+        if self.flat_mode:
+            opt.enable_flat_grads(self.grad_dtype)           # pinned staging + flat buffer: not allocatable during capture
+            opt._flat_g.zero_()
+        gc.collect()
+
+    def _eager_update(self):
+        """the update of a warm-up step, through the calls the captures make: all gradients -> the flat buffer, all-reduce,
+        clip + AdamW from it (flat mode), or clip + AdamW on the parameters' gradients"""
+        opt = self.optimizer
+        if self.flat_mode:
+            opt.enable_flat_grads(self.grad_dtype)
+            flat = opt.gather_grads()
+            if self.dp:
+                allreduce_mean(flat)
+            opt.step(max_norm=self.max_norm, from_flat=True)
+        else:
+            opt.step(max_norm=self.max_norm)
+        opt.zero_grad(set_to_none=True)
+
+    def _capture_tail(self, first, ema=None):
+        """(inside _scope, after the subclass captured ``first``: forward ... backward of segment 0) the graphs that follow it in a
+        call, from its pool: one per further segment of the backward, and in flat mode the optimizer graph (+ the EMA graph)"""
+        acc = self.accum_steps > 1
+        for k in range(1, len(self.segs or [])):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=first.pool(), **self._capture):
+                self.flat_parts.append(self._segment_backward(k, None, acc))
+            self.g_seg.append(g)
+        if self.flat_mode:
+            # the RCCL all-reduce(s) of the flat gradient buffer sit between the graphs; then the fused clip + AdamW reads the
+            # averaged (accumulated) gradients from the flat buffer
+            self.g_opt = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_opt, pool=first.pool(), **self._capture):
+                self.optimizer.step(max_norm=self.max_norm, from_flat=True)
+                if acc:
+                    self.optimizer._flat_g.zero_()           # the next micro-batch adds into an empty buffer
+            if ema is not None:
+                self.g_ema = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.g_ema, pool=first.pool(), **self._capture):
+                    ema.update()
+        torch.cuda.synchronize()
+        self.optimizer.flush_uploads()
+
     def _after_replay(self, check_finite):
+        """what follows the replay of the first graph(s) of a call: the rest of the flat-gradient schedule, then the non-finite poll"""
+        if self.g_opt is not None:
+            self._micro += 1
+            last = self._micro % self.accum_steps == 0        # reference engine.py:76 / :174: step on every accum_steps-th batch
+            works = []
+            if self.dp and last:                              # RCCL reduces segment k while the graphs of k+1.. run
+                works.append(allreduce_mean(self.flat_parts[0], async_op=True))
+            for k, g in enumerate(self.g_seg):
+                g.replay()
+                if self.dp and last:
+                    works.append(allreduce_mean(self.flat_parts[k + 1], async_op=True))
+            for w in works:
+                w.wait()
+            if last:
+                self.g_opt.replay()
+            if self.g_ema is not None and self._micro % self.ema_steps == 0:      # (:180: the EMA on its own period)
+                self.g_ema.replay()
         self._calls += 1
         if check_finite or (self.check_every and self._calls % self.check_every == 0):
             if self.nonfinite.item():                          # one 4-byte copy every `check_every` steps
@@ -373,9 +521,7 @@ class GraphedTrainStep(_GraphedBase):
                  max_norm=0.1, normalize=False, warmup=3, device_matching=True, max_targets=32, async_wgrad=False,
                  overlap_allreduce=True, coschedule=False, data_parallel=None, example_patches=None, fine_tune=False, fl=False,
                  ft_rand=None, mix_up_ratio=0.0, mix_alpha=1, max_events=20, accum_steps=1, dp_cuts='coarse', grad_dtype=None):
-        import gc
         from . import runtime
-        from .sedt import TargetTables
         if not isinstance(optimizer, FusedAdamW):
             raise RuntimeError('GraphedTrainStep needs FusedAdamW (device-side step count, one pointer table)')
         if (fine_tune or fl or mix_up_ratio) and not device_matching:
@@ -389,34 +535,17 @@ class GraphedTrainStep(_GraphedBase):
         self.runtime = runtime
         self.async_wgrad = async_wgrad
         self.coschedule = (coschedule or ops._dev_env('SEDT_COSCHEDULE', '0') == '1') and not async_wgrad
-        self.world = torch.distributed.get_world_size() if (torch.distributed.is_available()
-                                                            and torch.distributed.is_initialized()) else 1
-        self.accum_steps, self._micro = int(accum_steps), 0
-        if self.accum_steps < 1:
-            raise ValueError('accum_steps >= 1')
-        if self.accum_steps > 1 and not device_matching:
+        if int(accum_steps) > 1 and not device_matching:
             raise NotImplementedError('gradient accumulation is built for the device-matching graph')
-        if self.accum_steps > 1 and grad_dtype == torch.bfloat16:
-            raise ValueError('accumulating micro-batch gradients in a bf16 flat buffer loses them: use the f32 buffer')
-        # data_parallel=True forces the data-parallel schedule (flat gradients, all-reduce, optimizer graph) even in a
-        # one-process group: lets a single GPU exercise the RCCL calls of the multi-GPU path
-        self.dp = (self.world > 1) if data_parallel is None else bool(data_parallel)
-        if self.dp and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            raise RuntimeError('data_parallel=True needs an initialised torch.distributed process group')
+        self._setup_schedule(accum_steps, grad_dtype, data_parallel)
         net = getattr(model, 'module', model)
-        if self.world > 1:
-            broadcast_parameters(net)                         # replicas start identical (DDP does the same at wrap time)
-            runtime.seed_for_rank(torch.distributed.get_rank())   # ... but drop different elements (seeds are baked at capture)
-        # flat mode: gradients go through ONE flat buffer and the optimizer is its own graph (data parallel: the all-reduce sits
-        # in between; accumulation: micro-batches add into the buffer and only every accum_steps-th call runs the optimizer)
-        self.flat_mode = self.dp or self.accum_steps > 1
+        self._sync_replicas(net)
         if self.mix and mask_weak is None and self.flat_mode:
             # without a weak mask mixup_data DROPS clips on some draws (a merged pair without events, the unlabelled remainder:
             # utilities/mixup.py:104-122): such a batch cannot go through the captured schedule, and bailing out of it on ONE rank
             # in the middle of an epoch would leave the other ranks waiting in the collective.  Refused up front
             raise ValueError('mix-up under the data-parallel / accumulation schedule needs mask_weak (an empty slice(B, B) will do): '
                              'mixup_data then keeps the batch size on every draw')
-        self.grad_dtype = grad_dtype
         self._plan_segments(net, optimizer, dp_cuts if (self.dp and overlap_allreduce and device_matching) else 'none')
         dev = example_input.device
         self.dev = dev
@@ -431,37 +560,18 @@ class GraphedTrainStep(_GraphedBase):
             self.static_x = torch.empty_like(self.static_raw)
             self._jobs = _Upload(16 * self.static_raw.shape[0], dev)
             self._jobs.send(job_table([(i, 0, 1, 0.0) for i in range(self.static_raw.shape[0])]))     # identity until the first call
-        snap = _snapshot(net, optimizer)
-        side = train_stream(dev)
-        self._capture = dict(stream=side, **_CAPTURE)
-        side.wait_stream(torch.cuda.current_stream())
-        # gradients another stepper's captured backward left attached to the parameters would be ACCUMULATED into by the warm-up's
-        # eager backward (and the stack-level weight-gradient launches need fresh tensors: ops.defer_layer_wgrads)
-        optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.stream(side), optimizer.table_set(self._tabname), ops.defer_layer_wgrads():
-            for _ in range(warmup):                          # eager steps: lazy inits (LDS attributes, optimizer state)
-                if device_matching:
-                    self._eager_device_step(example_targets, max_targets)
-                else:
-                    train_step(model, criterion, optimizer, self.static_x, example_targets, mask_weak, mask_strong, max_norm,
-                               normalize, check_finite=False, allreduce=True, patches=self.static_patches)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        _restore(net, optimizer, snap)
-        self.nonfinite.zero_()
-        criterion.last_total = None      # drop the warm-up autograd graphs (their AccumulateGrad nodes belong to `side`)
-        optimizer.zero_grad(set_to_none=True)
-        if self.flat_mode:
-            optimizer.enable_flat_grads(grad_dtype)          # pinned staging + flat buffer: not allocatable during capture
-            optimizer._flat_g.zero_()
-        gc.collect()
-        quiesce_collectives(self.dev)
+
+        def warm():                                          # eager steps through the code the captures will run
+            if device_matching:
+                self._eager_device_step(example_targets, max_targets)
+            else:
+                train_step(model, criterion, optimizer, self.static_x, example_targets, mask_weak, mask_strong, max_norm,
+                           normalize, check_finite=False, allreduce=True, patches=self.static_patches)
+        self._warm_up(warm, warmup, net)
         self.device_matching = device_matching
         self.g_fwd = torch.cuda.CUDAGraph()
-        self.g_bwd = self.g_opt = None
-        self.g_seg, self.flat_parts = [], []
-        acc = self.accum_steps > 1
-        with optimizer.table_set(self._tabname), ops.defer_layer_wgrads():
+        self.g_bwd = None
+        with self._scope():
             if device_matching:
                 self.tables = self._make_tables(example_targets, max_targets)
                 with torch.cuda.graph(self.g_fwd, **self._capture):
@@ -473,14 +583,7 @@ class GraphedTrainStep(_GraphedBase):
                     else:
                         self.static_losses = self.criterion.compute(self.static_out, self.static_dense, self.fl)
                         self.static_total = self.criterion.last_total
-                        with self.runtime.async_wgrad(self.async_wgrad), ops.coschedule(self.coschedule):
-                            self.flat_parts.append(self._segment_backward(0, self.static_total, acc))
-                for k in range(1, len(self.segs or [])):          # one graph per further segment of the backward
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=self.g_fwd.pool(), **self._capture):
-                        with self.runtime.async_wgrad(self.async_wgrad), ops.coschedule(self.coschedule):
-                            self.flat_parts.append(self._segment_backward(k, None, acc))
-                    self.g_seg.append(g)
+                        self.flat_parts.append(self._segment_backward(0, self.static_total, self.accum_steps > 1))
             else:
                 with torch.cuda.graph(self.g_fwd, **self._capture):
                     self.static_out = self._forward()
@@ -491,16 +594,7 @@ class GraphedTrainStep(_GraphedBase):
                 self.g_bwd = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.g_bwd, pool=self.g_fwd.pool(), **self._capture):
                     self._backward_and_step()
-            if self.flat_mode:
-                # the RCCL all-reduce(s) of the flat gradient buffer sit between the graphs; then the fused clip + AdamW reads
-                # the averaged (accumulated) gradients from the flat buffer
-                self.g_opt = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_opt, pool=self.g_fwd.pool(), **self._capture):
-                    optimizer.step(max_norm=max_norm, from_flat=True)
-                    if acc:
-                        optimizer._flat_g.zero_()            # the next micro-batch adds into an empty buffer
-        torch.cuda.synchronize()
-        optimizer.flush_uploads()
+            self._capture_tail(self.g_fwd)
 
     # ------------------------------------------------------------------ pieces
     def _make_tables(self, example_targets, max_targets):
@@ -532,15 +626,11 @@ class GraphedTrainStep(_GraphedBase):
         total = self.criterion.last_total
         self.criterion.last_total = None
         torch.autograd.backward(total, grad_tensors=self._root_grad(total))
-        if self.flat_mode:
-            self.optimizer.enable_flat_grads(self.grad_dtype)
-            flat = self.optimizer.gather_grads()
-            if self.dp:
-                allreduce_mean(flat)
-            self.optimizer.step(max_norm=self.max_norm, from_flat=True)
-        else:
-            self.optimizer.step(max_norm=self.max_norm)
-        self.optimizer.zero_grad(set_to_none=True)
+        self._eager_update()
+
+    def _segment_backward(self, k, root=None, accumulate=False):
+        with self.runtime.async_wgrad(self.async_wgrad), ops.coschedule(self.coschedule):      # (as in _backward_and_step)
+            return super()._segment_backward(k, root, accumulate)
 
     def _backward_and_step(self):
         self.static_losses = self.criterion.compute(self.static_out, self.static_dense, self.fl)
@@ -591,23 +681,8 @@ class GraphedTrainStep(_GraphedBase):
                 raise RuntimeError(f'batch composition changed: captured {self.meta}, got {dense["_meta"]}')
             self.static_pack.copy_(dense['_pack'], non_blocking=True)
             self.g_bwd.replay()
-        if self.g_opt is not None:
-            self._micro += 1
-            last = self._micro % self.accum_steps == 0        # (engine.py:76: step on every accum_steps-th batch)
-            works = []
-            if self.dp and last:                              # RCCL reduces segment k while the graphs of k+1.. run
-                works.append(allreduce_mean(self.flat_parts[0], async_op=True))
-            for k, g in enumerate(self.g_seg):
-                g.replay()
-                if self.dp and last:
-                    works.append(allreduce_mean(self.flat_parts[k + 1], async_op=True))
-            for w in works:
-                w.wait()
-            if last:
-                self.g_opt.replay()
         self._after_replay(check_finite)
         return self.static_total, self.static_losses
-
 
     def _eager_batch(self, batch_input, targets, patches=None):
         """one batch the captured graph cannot take, through engine.train_step on the training stream (same optimizer state: the
@@ -617,14 +692,9 @@ class GraphedTrainStep(_GraphedBase):
                                       'pass mask_weak (mixup_data then keeps the batch size) or use the eager train_step')
         # the captured backward leaves its (static) gradient tensors attached to the parameters: an eager backward would ADD to them
         self.optimizer.zero_grad(set_to_none=True)
-        side, cur = train_stream(self.dev), torch.cuda.current_stream(self.dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            out = train_step(self.model, self.criterion, self.optimizer, batch_input, targets, self.mw, self.ms, self.max_norm,
-                             self.normalize, check_finite=True, patches=patches, fine_tune=self.fine_tune, fl=self.fl,
-                             mix_up_ratio=self.mix)
-        cur.wait_stream(side)
-        return out
+        return _on_train_stream(self.dev, train_step, self.model, self.criterion, self.optimizer, batch_input, targets, self.mw, self.ms,
+                                self.max_norm, self.normalize, check_finite=True, patches=patches, fine_tune=self.fine_tune,
+                                fl=self.fl, mix_up_ratio=self.mix)
 
 
 def broadcast_parameters(model, src=0):
@@ -709,20 +779,13 @@ class GraphedPredictStep(object):
             self.clip_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.metrics_gen = metrics.generation
             saved = [t.clone() for t in metrics.counters()]            # the warm-up runs count too: put the counters back after
-        stream = train_stream(dev)
-        stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(stream):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(stream)
-        torch.cuda.synchronize()
+        _warm_on_train_stream(dev, self._body, warmup)
         if metrics is not None:
             for t, s in zip(metrics.counters(), saved):
                 t.copy_(s)
             torch.cuda.synchronize()
-        quiesce_collectives(dev)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=stream, **_CAPTURE):
+        with torch.cuda.graph(self.graph, stream=train_stream(dev), **_CAPTURE):
             self.out = self._body()
         torch.cuda.synchronize()
 
@@ -818,14 +881,9 @@ def semi_train_step(model, ema, criterion, optimizer, batch_input_teacher, batch
     targets returned are then the mixed ones (what the student's criterion saw)."""
     dev = _tensors(batch_input_teacher).device
     if dev.type == 'cuda' and torch.cuda.current_stream(dev) == torch.cuda.default_stream(dev):
-        side, cur = train_stream(dev), torch.cuda.current_stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            out = semi_train_step(model, ema, criterion, optimizer, batch_input_teacher, batch_input_student, targets, mask_strong,
-                                  mask_weak, mask_label, mask_unlabel, classwise_threshold, fine_tune, normalize, fl, max_norm,
-                                  counter, check_finite, do_step, do_ema, mix_up_ratio)
-        cur.wait_stream(side)
-        return out
+        return _on_train_stream(dev, semi_train_step, model, ema, criterion, optimizer, batch_input_teacher, batch_input_student,
+                                targets, mask_strong, mask_weak, mask_label, mask_unlabel, classwise_threshold, fine_tune, normalize,
+                                fl, max_norm, counter, check_finite, do_step, do_ema, mix_up_ratio)
     xt, xs = _tensors(batch_input_teacher), _tensors(batch_input_student)
     wd = criterion.weight_dict
     x_lab, t_lab = xt[mask_label], targets[mask_label]
@@ -918,7 +976,10 @@ class GraphedSemiStep(_GraphedBase):
 
     The thresholds (``classwise_threshold``, f32 [C] on the device) are read by the graph on every replay: update them in
     place (``stepper.threshold.copy_(...)``) when the driver adjusts them per epoch (train_ss_sedt.py:207).
-    ``counter`` (int32 [C]) accumulates the pseudo events per class like the reference's pseudo_labels_counter."""
+    ``counter`` (int32 [C]) accumulates the pseudo events per class like the reference's pseudo_labels_counter.
+
+    ``fuse_student_forwards=False`` keeps the labelled and the unlabelled student clips as two forwards (the reference's order of
+    work); the layers' weight gradients are then not deferred (ops.defer_layer_wgrads needs one contribution per parameter)."""
 
     def __init__(self, *args, **kw):
         try:
@@ -930,16 +991,11 @@ class GraphedSemiStep(_GraphedBase):
                  mask_unlabel, classwise_threshold, orig_size=10.0, fine_tune=False, normalize=False, fl=False, max_norm=0.1,
                  warmup=2, max_targets=32, accumulating_ema_steps=1, fuse_student_forwards=True, mix_up_ratio=0.0, mix_alpha=1,
                  max_events=20, accum_steps=1, overlap_allreduce=True, dp_cuts='coarse', grad_dtype=None, data_parallel=None):
-        import gc
         from . import runtime
         from .sedt import TargetTables
         if not isinstance(optimizer, FusedAdamW):
             raise RuntimeError('GraphedSemiStep needs FusedAdamW')
-        self.accum_steps, self.ema_steps, self._micro = int(accum_steps), int(accumulating_ema_steps), 0
-        if self.accum_steps < 1 or self.ema_steps < 1:
-            raise ValueError('accum_steps / accumulating_ema_steps >= 1')
-        if self.accum_steps > 1 and grad_dtype == torch.bfloat16:
-            raise ValueError('accumulating micro-batch gradients in a bf16 flat buffer loses them: use the f32 buffer')
+        self._setup_schedule(accum_steps, grad_dtype, data_parallel, ema_steps=accumulating_ema_steps)
         self.model, self.ema, self.criterion, self.optimizer, self.runtime = model, ema, criterion, optimizer, runtime
         self.ms, self.mw, self.ml, self.mu = mask_strong, mask_weak, mask_label, mask_unlabel
         self.flags = dict(normalize=normalize, fine_tune=fine_tune, fl=fl)
@@ -953,24 +1009,8 @@ class GraphedSemiStep(_GraphedBase):
         dev = xt.device
         self.dev = dev
         self._init_common(criterion, optimizer, dev)
-        dist = torch.distributed
-        self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-        self.dp = (self.world > 1) if data_parallel is None else bool(data_parallel)
-        if self.dp and not (dist.is_available() and dist.is_initialized()):
-            raise RuntimeError('data_parallel=True needs an initialised torch.distributed process group')
-        # flat mode (see GraphedTrainStep): gradients through the flat buffer, optimizer (and EMA update) as graphs of their own
-        self.flat_mode = self.dp or self.accum_steps > 1 or self.ema_steps > 1
-        self.grad_dtype = grad_dtype
         self._plan_segments(model, optimizer, dp_cuts if (self.dp and overlap_allreduce and fuse_student_forwards) else 'none')
-        if self.world > 1:
-            broadcast_parameters(model)
-            with torch.no_grad():
-                for n, p in model.named_parameters():         # the teacher starts identical on every rank too
-                    if n in ema.shadow:
-                        h = ema.shadow[n] if dist.get_backend() == 'nccl' else ema.shadow[n].cpu()
-                        dist.broadcast(h, 0)
-                        ema.shadow[n].copy_(h)
-            runtime.seed_for_rank(dist.get_rank())
+        self._sync_replicas(model, ema)
         n_lab_clips = xt[mask_label].shape[0]
         self.x_cat = torch.cat([xt[mask_label], xs[mask_unlabel]])          # static input of the student forward(s)
         self.x_lab, self.x_stu = self.x_cat[:n_lab_clips], self.x_cat[n_lab_clips:]
@@ -1002,56 +1042,23 @@ class GraphedSemiStep(_GraphedBase):
             self._lam_u = _Upload(8, dev)
             self._lam_u.send(torch.from_numpy(np.asarray([1.0, 0.0], np.float32).view(np.uint8).copy()))
             self.jobs_u = torch.zeros(16 * n_u, dtype=torch.uint8, device=dev)
-        snap = _snapshot(model, optimizer, ema)
-        side = train_stream(dev)
-        self._capture = dict(stream=side, **_CAPTURE)
-        side.wait_stream(torch.cuda.current_stream())
-        optimizer.zero_grad(set_to_none=True)                 # (see GraphedTrainStep: no stale .grad under the warm-up's eager backward)
-        with torch.cuda.stream(side), optimizer.table_set(self._tabname), ops.defer_layer_wgrads():
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        _restore(model, optimizer, snap, ema)
-        self.nonfinite.zero_()
+
+        def warm():
+            # every handle on a warm-up autograd graph is dropped with its step: the AccumulateGrad nodes belong to the training
+            # stream; kept alive, the captured backward would accumulate the two forwards' gradients outside the capture's ordering
+            self._body()
+            self.sup = self.unsup = self.total = None
+        # two student forwards give every decoder parameter TWO gradient contributions per backward: no deferral of the layers'
+        # weight gradients then (the second would be summed into a first that is not written yet)
+        self._warm_up(warm, warmup, model, ema, defer=self.fuse)
         self.counter.zero_()
-        # drop every handle on the warm-up autograd graphs: their AccumulateGrad nodes belong to `side`; kept alive, the
-        # captured backward would accumulate the two forwards' gradients on that stream, outside the capture's ordering
-        criterion.last_total = None
-        self.sup = self.unsup = self.total = None
-        optimizer.zero_grad(set_to_none=True)
-        gc.collect()
-        quiesce_collectives(self.dev)
-        if self.flat_mode:
-            optimizer.enable_flat_grads(grad_dtype)
-            optimizer._flat_g.zero_()
         self.graph = torch.cuda.CUDAGraph()
-        self.g_opt = self.g_ema = None
-        self.g_seg, self.flat_parts = [], []
-        with optimizer.table_set(self._tabname), ops.defer_layer_wgrads():
+        with self._scope():
             with torch.cuda.graph(self.graph, **self._capture):
                 self._body(part='fwd_bwd' if self.flat_mode else 'all')
-            for k in range(1, len(self.segs or [])):          # data parallel: one graph per further segment of the backward
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self.graph.pool(), **self._capture):
-                    self.flat_parts.append(self._segment_backward(k, None, self.accum_steps > 1))
-                self.g_seg.append(g)
-            if self.flat_mode:                                # (RCCL all-reduces of the flat gradient segments in between)
-                self.g_opt = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_opt, pool=self.graph.pool(), **self._capture):
-                    self._body(part='update')
-                self.g_ema = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_ema, pool=self.graph.pool(), **self._capture):
-                    self.ema.update()
-        torch.cuda.synchronize()
-        optimizer.flush_uploads()
+            self._capture_tail(self.graph, ema)
 
     def _body(self, part='all'):
-        if part == 'update':
-            self.optimizer.step(max_norm=self.max_norm, from_flat=True)
-            if self.accum_steps > 1:
-                self.optimizer._flat_g.zero_()
-            return
         crit, model = self.criterion, self.model
         if self.mix:
             ops.mixup(self.x_lab_raw, self.x_lab_raw, self._jobs_l.dev_buf, out=self.x_lab)
@@ -1090,15 +1097,7 @@ class GraphedSemiStep(_GraphedBase):
         if part == 'fwd_bwd':
             self.flat_parts = [self.optimizer.gather_grads(accumulate=self.accum_steps > 1)]
             return
-        if self.flat_mode:                                    # (eager warm-up of the flat-buffer schedule)
-            self.optimizer.enable_flat_grads(self.grad_dtype)
-            flat = self.optimizer.gather_grads()
-            if self.dp:
-                allreduce_mean(flat)
-            self.optimizer.step(max_norm=self.max_norm, from_flat=True)
-        else:
-            self.optimizer.step(max_norm=self.max_norm)
-        self.optimizer.zero_grad(set_to_none=True)
+        self._eager_update()                                  # (flat mode: the eager warm-up of the flat-buffer schedule)
         self.ema.update()
 
     def __call__(self, x_teacher, x_student, targets, check_finite=False):
@@ -1123,21 +1122,5 @@ class GraphedSemiStep(_GraphedBase):
             self.runtime.bump_seed(self.dev)
         self._before_replay()
         self.graph.replay()
-        if self.g_opt is not None:
-            self._micro += 1
-            last = self._micro % self.accum_steps == 0        # engine.py:174 / :180: optimizer and EMA on their own periods
-            works = []
-            if self.dp and last:
-                works.append(allreduce_mean(self.flat_parts[0], async_op=True))
-            for k, g in enumerate(self.g_seg):
-                g.replay()
-                if self.dp and last:
-                    works.append(allreduce_mean(self.flat_parts[k + 1], async_op=True))
-            for w in works:
-                w.wait()
-            if last:
-                self.g_opt.replay()
-            if self._micro % self.ema_steps == 0:
-                self.g_ema.replay()
         self._after_replay(check_finite)
         return self.total, self.sup, self.unsup

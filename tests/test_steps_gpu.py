@@ -133,10 +133,12 @@ def _rand_semi_batch(seed, n_strong, n_weak, n_unl, T=496):
     return x_t.cuda(), x_s.cuda(), _cuda_targets(t)
 
 
-def test_graphed_semi_step_matches_eager_and_follows_live_parameters(pkg):
+@pytest.mark.parametrize('fuse_student_forwards', [True, False])
+def test_graphed_semi_step_matches_eager_and_follows_live_parameters(pkg, fuse_student_forwards):
     """GraphedSemiStep (ONE graph: 3 forwards, device pseudo labels, device matching, backward, AdamW, EMA) reproduces the
     eager semi_train_step on changing batches; constructing it leaves the training state untouched; and - SURVEY H5 - a
-    state_dict loaded AFTER the capture (student) and new teacher weights (in place) are what the next replay uses"""
+    state_dict loaded AFTER the capture (student) and new teacher weights (in place) are what the next replay uses.
+    fuse_student_forwards=False: the labelled and the unlabelled student clips as two forwards, as the eager step runs them"""
     runtime, sedt = pkg
     from sound_event_detection_transformer_amd.engine import semi_train_step, GraphedSemiStep
     runtime.set_compute_dtype('bf16')
@@ -154,7 +156,7 @@ def test_graphed_semi_step_matches_eager_and_follows_live_parameters(pkg):
             sd0 = {k: v.clone() for k, v in model.state_dict().items()}
             sh0 = {k: v.clone() for k, v in ema.shadow.items()}
             stepper = GraphedSemiStep(model, ema, crit, opt, batches[0][0], batches[0][1], batches[0][2],
-                                      classwise_threshold=thr, **masks)
+                                      classwise_threshold=thr, fuse_student_forwards=fuse_student_forwards, **masks)
             for k, v in model.state_dict().items():                       # capture + warm-up restored everything
                 assert torch.equal(v, sd0[k]), k
             for k, v in ema.shadow.items():
