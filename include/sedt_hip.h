@@ -137,7 +137,7 @@ typedef struct SedtIgemm {
 
 int sedt_igemm(const SedtIgemm* args, int dtype, void* stream);
 /* sizeof of an argument struct as THIS library was compiled (0 SedtIgemm, 1 SedtReduceJob, 2 SedtSplitJob, 3 SedtPrefetch, 4 SedtCriterion,
- * 5 SedtMatch, 6 SedtChunk, 7 SedtBnJob, 8 SedtPackJob, 9 SedtFragJob, 10 SedtPoolAt, 11 SedtCopyJob; -1 otherwise): lets a binding verify its mirror of the structs */
+ * 5 SedtMatch, 6 SedtChunk, 7 SedtBnJob, 8 SedtPackJob, 9 SedtFragJob, 10 SedtPoolAt, 11 SedtCopyJob, 12 SedtViewAug; -1 otherwise): lets a binding verify its mirror of the structs */
 int sedt_sizeof(int which);
 /* njobs (<= 8 per launch) independent trans == 0 problems - e.g. the q / k / v projections of an attention block; one
  * launch when every problem resolves to the 64x64 2-stage bf16 kernel, otherwise njobs sedt_igemm calls.  HOST array. */
@@ -792,6 +792,45 @@ int sedt_event_segment_metrics_update(const float* scores, const int64_t* labels
 int sedt_box_transform(const float* amp, int64_t raw_stride, const void* aug, const double* mean, const double* stdv, int B,
                        int frames, int F, int apply_log, int fill_mean, float fill_const, float* out, void* stream);
 int sedt_mixup(const float* x1, const float* x2, const void* jobs, int n_out, int64_t clip_elems, float* out, void* stream);
+/* sedt_box_transform_views: BOTH views of the mean-teacher recipe from ONE raw clip in one launch - what the reference's noisy chain
+ * (get_transforms(noise_dict_params={"mean": 0., "snr": snr}, ...), train_ss_sedt.py:87-97) makes of a clip: AugmentGaussianNoise
+ * (BoxTransforms.py:121-180) turns it into the pair (data, noisy data), every later transform then runs on both members with its own
+ * random draw (TimeMask skips member 0).  aug = B records SedtViewAug: the sedt_box_transform record of view 0 (teacher) and of view 1
+ * (student; both carry the same nframes_raw) and the noise decision of the clip.
+ *   view 1 of a clip with noise_on: x + sd[band] * z, sd[band] = sqrt(mean over ALL nframes_raw raw rows of x^2 * 10^(-snr_db / 10))
+ *   in f32 (a band of zeros: sd = 0, no noise), each band summed in a fixed order; then, per view with its own record, exactly the
+ *   chain and the arithmetic of sedt_box_transform (the 80 dB floor hangs from that view's own maximum).  View 0, and view 1 of a
+ *   clip with noise_on = 0, are bit-identical to sedt_box_transform run with that view's record.
+ * z, one STANDARD normal per raw element, comes from one of two sources:
+ *   injected  z != null: f32 [B][raw_stride][F], laid out like amp (rows >= nframes_raw ignored; the kernel scales it by sd) - how a
+ *             test replays the reference's np.random.normal draw;
+ *   drawn     z == null: counter-based.  Element (clip b of the launch, raw row t, band c) has the stream index
+ *             e = offset + (b * raw_stride + t) * F + c (F and offset even); the elements 2p, 2p + 1 share one Box-Muller pair of
+ *             a = rng32(s, 2p), b = rng32(s, 2p + 1), s = seed + (seed_ptr ? *seed_ptr : 0), rng32 the hash of the dropout
+ *             kernels: u1 = ((a >> 8) + 1) * 2^-24 in (0, 1], u2 = (b >> 8) * 2^-24, r = sqrt(-2 ln u1),
+ *             z[2p] = r cos(2 pi u2), z[2p + 1] = r sin(2 pi u2).  The top 24 bits of each hash make u1, u2 exact in f32, so the
+ *             device stream equals a float64 restatement from the same integers to the rounding of logf / sincospif (|z| <= 5.77).
+ *             The caller advances `offset` by B * raw_stride * F per call; seed_ptr lets a captured launch take a device word
+ *             the step itself advances.
+ * Grid (B, 2): one workgroup per (clip, view), the view stays in LDS between the passes like sedt_box_transform; the workgroup of
+ * a noisy view reads the raw clip twice (band sums, then the chain; the second read comes from L2 / Infinity Cache).
+ * amp [B][raw_stride][F] f32, out0 / out1 [B][1][frames][F] f32. */
+typedef struct {
+  int32_t nframes_raw;    /* rows of the raw clip actually present */
+  int32_t tm_t, tm_t0;    /* time mask: rows [tm_t0, tm_t0 + tm_t) zeroed (tm_t = 0: off) */
+  int32_t fm_f, fm_f0;    /* frequency mask: bands [fm_f0, fm_f0 + fm_f) overwritten if fm_on */
+  int32_t fm_on;
+  int32_t fs_shift;       /* frequency shift in bands (0: off) */
+  int32_t pad_;
+} SedtClipAug;            /* the record of sedt_box_transform */
+typedef struct {
+  SedtClipAug view[2];    /* 0: teacher / labelled pass, 1: student */
+  int32_t noise_on;       /* 1: view 1 starts from x + sd * z, 0: from the same data as view 0 */
+  int32_t pad_;
+} SedtViewAug;            /* sedt_sizeof index 12 */
+int sedt_box_transform_views(const float* amp, int64_t raw_stride, const void* aug, const double* mean, const double* stdv, int B,
+                             int frames, int F, int apply_log, int fill_mean, float fill_const, float snr_db, const float* z,
+                             uint32_t seed, const uint32_t* seed_ptr, uint64_t offset, float* out0, float* out1, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

@@ -1,4 +1,6 @@
 // input.hip - the input side of the training step on the device:
+//   * box_transform_views_kernel  the same chain for BOTH mean-teacher views of a clip in one launch, the student's Gaussian noise
+//                           (AugmentGaussianNoise :121-180) drawn in the kernel or injected
 //   * box_transform_kernel  the per-clip feature transforms of reference utilities/BoxTransforms.py composed as
 //                           get_transforms does (:454-490): ApplyLog (librosa.amplitude_to_db, :55-67) -> PadOrTrunc (:70-117)
 //                           -> TimeMask (:363-395) -> FreqMask(fill "mean" or constant, :398-425) -> FreqShift (:428-451)
@@ -6,20 +8,17 @@
 //   * mixup_kernel          the feature half of utilities/mixup.py:13-196 (lam * x1 + (1 - lam) * x2, or one of the two)
 // One workgroup per clip: the clip (frames x 64 mel, <= 127 KB as f32) lives in LDS between the passes, so HBM sees one read
 // of the raw amplitudes and one write of the normalised features.  Random parameters are drawn on the HOST exactly as the
-// reference draws them (np.random, same order) and arrive as integers: the kernel is deterministic.
+// reference draws them (np.random, same order) and arrive as integers: the kernel is deterministic.  The one exception is the
+// student view's Gaussian noise: 2 M normals per C5 batch come from a counter-based stream inside the kernel (a function of seed and
+// element index alone, so still reproducible), or are injected.
 #include <algorithm>
+#include <cmath>
 #include "common.h"
 
 namespace sedt {
 
-struct ClipAug {               // mirrors utilities/transforms.py:_AUG (8 x int32 per clip)
-  int32_t nframes_raw;         // frames of the raw clip (rows of amp actually present)
-  int32_t tm_t, tm_t0;         // time mask: rows [t0, t0 + t) are zeroed (t = 0: off)
-  int32_t fm_f, fm_f0;         // frequency mask: mel bands [f0, f0 + f) are overwritten (f = 0 with fm_on = 0: off)
-  int32_t fm_on;               // 1 = apply (f may be 0: numpy then writes nothing)
-  int32_t fs_shift;            // frequency shift in bands (0 = off)
-  int32_t pad_;
-};
+typedef SedtClipAug ClipAug;    // mirrors utilities/transforms.py:_AUG (8 x int32 per clip; include/sedt_hip.h)
+typedef SedtViewAug ViewAug;    // mirrors utilities/transforms.py:_VAUG (the records of the two views + the noise decision)
 
 __device__ __forceinline__ float block_max(float v, float* red) {
   v = wave_max(v);
@@ -40,26 +39,18 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return s;
 }
 
-// amp [B][raw_stride][F] f32 mel amplitudes (rows >= nframes_raw are ignored), out [B][1][frames][F] f32
-__global__ __launch_bounds__(1024) void box_transform_kernel(const float* __restrict__ amp, long raw_stride, const ClipAug* __restrict__ aug,
-                                                             const double* __restrict__ mean, const double* __restrict__ stdv,
-                                                             int frames, int F, int apply_log, int fill_mean, float fill_const,
-                                                             float* __restrict__ out) {
-  extern __shared__ float lds[];
-  float* clip = lds;                              // [frames][F]
-  float* red = lds + (long)frames * F;            // [16]
-  const int b = blockIdx.x, t = threadIdx.x;
-  const ClipAug a = aug[b];
-  const float* src = amp + (long)b * raw_stride * F;
-  const int nraw = a.nframes_raw;
-  // ---- pass 1: amplitude -> dB (10 log10(max(1e-10, x^2)), reference value 1.0), clip maximum over ALL raw frames
-  float mx = -INFINITY;
-  for (long i = t; i < (long)nraw * F; i += 1024) {
-    const float x = src[i];
-    const float v = apply_log ? 10.f * log10f(fmaxf(1e-10f, x * x)) : x;
-    mx = fmaxf(mx, v);
-    if (i < (long)frames * F) clip[i] = v;
-  }
+// pass 1 of one element: amplitude -> dB (10 log10(max(1e-10, x^2)), reference value 1.0); the rows PadOrTrunc keeps go to LDS
+__device__ __forceinline__ float to_db_keep(float x, long i, int apply_log, long nkeep, float* clip) {
+  const float v = apply_log ? 10.f * log10f(fmaxf(1e-10f, x * x)) : x;
+  if (i < nkeep) clip[i] = v;
+  return v;
+}
+
+// everything after pass 1 of one clip (one workgroup of 1024): mx = this thread's maximum over the raw elements it converted
+__device__ __forceinline__ void box_transform_tail(float mx, const ClipAug a, const double* __restrict__ mean, const double* __restrict__ stdv,
+                                                   int frames, int F, int apply_log, int fill_mean, float fill_const,
+                                                   float* __restrict__ dst, float* clip, float* red) {
+  const int t = threadIdx.x, nraw = a.nframes_raw;
   for (long i = (long)nraw * F + t; i < (long)frames * F; i += 1024) clip[i] = 0.f;        // PadOrTrunc: zero rows appended
   mx = block_max(mx, red);
   __syncthreads();
@@ -94,7 +85,6 @@ __global__ __launch_bounds__(1024) void box_transform_kernel(const float* __rest
     __syncthreads();
   }
   // ---- frequency shift (np.roll along mel, wrapped bands zeroed) + normalisation (float64 like Scaler.normalize), store
-  float* dst = out + (long)b * frames * F;
   const int sh = a.fs_shift;
   for (long i = t; i < (long)frames * F; i += 1024) {
     const int r = (int)(i / F), c = (int)(i - (long)r * F);
@@ -102,6 +92,96 @@ __global__ __launch_bounds__(1024) void box_transform_kernel(const float* __rest
     const float v = (cs >= 0 && cs < F) ? clip[(long)r * F + cs] : 0.f;
     dst[i] = mean ? (float)(((double)v - mean[c]) / stdv[c]) : v;
   }
+}
+
+// amp [B][raw_stride][F] f32 mel amplitudes (rows >= nframes_raw are ignored), out [B][1][frames][F] f32
+__global__ __launch_bounds__(1024) void box_transform_kernel(const float* __restrict__ amp, long raw_stride, const ClipAug* __restrict__ aug,
+                                                             const double* __restrict__ mean, const double* __restrict__ stdv,
+                                                             int frames, int F, int apply_log, int fill_mean, float fill_const,
+                                                             float* __restrict__ out) {
+  extern __shared__ float lds[];
+  float* clip = lds;                              // [frames][F]
+  float* red = lds + (long)frames * F;            // [16]
+  const int b = blockIdx.x, t = threadIdx.x;
+  const ClipAug a = aug[b];
+  const float* src = amp + (long)b * raw_stride * F;
+  // ---- pass 1: amplitude -> dB, clip maximum over ALL raw frames
+  float mx = -INFINITY;
+  for (long i = t; i < (long)a.nframes_raw * F; i += 1024) mx = fmaxf(mx, to_db_keep(src[i], i, apply_log, (long)frames * F, clip));
+  box_transform_tail(mx, a, mean, stdv, frames, F, apply_log, fill_mean, fill_const, out + (long)b * frames * F, clip, red);
+}
+
+// ---- the two views of the mean-teacher recipe from one raw clip (reference utilities/BoxTransforms.py:121-180 AugmentGaussianNoise
+// at the head of the chain, Transform._apply_transform :19-35 running every later transform on both members).
+// One standard-normal pair of the counter-based stream (include/sedt_hip.h: sedt_box_transform_views): e2 = even stream index.
+__device__ __forceinline__ void normal_pair(uint32_t seed, uint64_t e2, float& z0, float& z1) {
+  const uint32_t ha = rng32(seed, e2), hb = rng32(seed, e2 + 1);
+  const float u1 = (float)((ha >> 8) + 1u) * 0x1p-24f;        // (0, 1], exact in f32: never 0
+  const float u2 = (float)(hb >> 8) * 0x1p-24f;               // [0, 1), exact
+  const float r = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincospif(2.f * u2, &sn, &cs);
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
+// grid (B, 2): workgroup (b, k) makes view k of clip b.  Only the workgroup of a noisy view 1 takes the two extra steps (band sums,
+// noise); every other one runs the single-view kernel's own code on its record.
+__global__ __launch_bounds__(1024) void box_transform_views_kernel(const float* __restrict__ amp, long raw_stride, const ViewAug* __restrict__ aug,
+                                                                   const double* __restrict__ mean, const double* __restrict__ stdv,
+                                                                   int frames, int F, int apply_log, int fill_mean, float fill_const,
+                                                                   float noise_pow, const float* __restrict__ zin, uint32_t seed,
+                                                                   const uint32_t* __restrict__ seed_ptr, uint64_t offset,
+                                                                   float* __restrict__ out0, float* __restrict__ out1) {
+  extern __shared__ float lds[];
+  float* clip = lds;                              // [frames][F]
+  float* red = lds + (long)frames * F;            // [16]
+  float* sd = red + 16;                           // [F] noise std per band
+  float* part = sd + F;                           // [1024 / F][F] partial band sums
+  const int b = blockIdx.x, k = blockIdx.y, t = threadIdx.x;
+  const ClipAug a = aug[b].view[k];
+  const bool noisy = k == 1 && aug[b].noise_on != 0;
+  const long base = (long)b * raw_stride * F;
+  const float* src = amp + base;
+  const long nel = (long)a.nframes_raw * F;
+  float mx = -INFINITY;
+  if (!noisy) {
+    for (long i = t; i < nel; i += 1024) mx = fmaxf(mx, to_db_keep(src[i], i, apply_log, (long)frames * F, clip));
+  } else {
+    // ---- band sums over ALL raw rows in a fixed order: thread (g, c) adds rows g, g + G, ... of band c, then band c adds its G partials
+    const int G = 1024 / F, g = t / F, c = t - g * F;
+    if (g < G) {
+      float s = 0.f;
+      for (int r = g; r < a.nframes_raw; r += G) {
+        const float x = src[(long)r * F + c];
+        s += (x * x) * noise_pow;
+      }
+      part[g * F + c] = s;
+    }
+    __syncthreads();
+    if (t < F) {
+      float s = 0.f;
+      for (int q = 0; q < G; ++q) s += part[q * F + t];
+      sd[t] = sqrtf(s / (float)a.nframes_raw);
+    }
+    __syncthreads();
+    // ---- pass 1 on x + sd[band] * z, two neighbouring elements (one Box-Muller pair) per thread and trip; nel is even
+    const uint32_t s32 = eff_seed(seed, seed_ptr);
+    for (long i = 2L * t; i < nel; i += 2048) {
+      const float2 x = *reinterpret_cast<const float2*>(src + i);
+      float z0, z1;
+      if (zin) {
+        const float2 z = *reinterpret_cast<const float2*>(zin + base + i);
+        z0 = z.x; z1 = z.y;
+      } else {
+        normal_pair(s32, offset + (uint64_t)(base + i), z0, z1);
+      }
+      const int c0 = (int)(i % F);
+      mx = fmaxf(mx, to_db_keep(x.x + sd[c0] * z0, i, apply_log, (long)frames * F, clip));
+      mx = fmaxf(mx, to_db_keep(x.y + sd[c0 + 1] * z1, i + 1, apply_log, (long)frames * F, clip));
+    }
+  }
+  box_transform_tail(mx, a, mean, stdv, frames, F, apply_log, fill_mean, fill_const, (k ? out1 : out0) + (long)b * frames * F, clip, red);
 }
 
 struct MixJob {                // mirrors utilities/mixup.py (4 x int32 + 1 float per output clip)
@@ -335,6 +415,29 @@ extern "C" int sedt_box_transform(const float* amp, int64_t raw_stride, const vo
   hipLaunchKernelGGL(box_transform_kernel, dim3(B), dim3(1024), lds, reinterpret_cast<hipStream_t>(stream), amp, (long)raw_stride,
                      reinterpret_cast<const ClipAug*>(aug), mean, stdv, frames, F, apply_log, fill_mean, fill_const, out);
   return check_launch("box_transform");
+}
+
+extern "C" int sedt_box_transform_views(const float* amp, int64_t raw_stride, const void* aug, const double* mean, const double* stdv,
+                                        int B, int frames, int F, int apply_log, int fill_mean, float fill_const, float snr_db,
+                                        const float* z, uint32_t seed, const uint32_t* seed_ptr, uint64_t offset, float* out0,
+                                        float* out1, void* stream) {
+  using namespace sedt;
+  SEDT_REQUIRE(amp && aug && out0 && out1, "box_transform_views: null pointer");
+  SEDT_REQUIRE((mean == nullptr) == (stdv == nullptr), "box_transform_views: mean and std go together");
+  SEDT_REQUIRE(B >= 0 && frames >= 1 && F >= 2 && F <= 1024 && raw_stride >= 1, "box_transform_views: B=%d frames=%d F=%d", B, frames, F);
+  SEDT_REQUIRE(F % 2 == 0 && offset % 2 == 0, "box_transform_views: F=%d and the stream offset must be even (normals come in pairs)", F);
+  const size_t lds = ((size_t)frames * F + 16 + F + (size_t)(1024 / F) * F) * sizeof(float);
+  SEDT_REQUIRE(lds <= 160 * 1024, "box_transform_views: a clip of %d x %d f32 does not fit the 160 KB LDS", frames, F);
+  if (B == 0) return 0;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(box_transform_views_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  hipLaunchKernelGGL(box_transform_views_kernel, dim3(B, 2), dim3(1024), lds, reinterpret_cast<hipStream_t>(stream), amp, (long)raw_stride,
+                     reinterpret_cast<const ViewAug*>(aug), mean, stdv, frames, F, apply_log, fill_mean, fill_const,
+                     (float)pow(10.0, -(double)snr_db / 10.0), z, seed, seed_ptr, offset, out0, out1);
+  return check_launch("box_transform_views");
 }
 
 extern "C" int sedt_mixup(const float* x1, const float* x2, const void* jobs, int n_out, int64_t clip_elems, float* out, void* stream) {

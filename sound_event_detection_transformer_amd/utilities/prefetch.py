@@ -11,7 +11,8 @@ from .utils import NestedTensor
 class DevicePrefetcher(object):
     def __init__(self, loader, device='cuda', transform=None, return_indexes=False, slots=2, targets_to_device=True):
         """loader yields (input, targets) [or ((input, targets), index)]: input = NestedTensor / tensor of features, or - with
-        ``transform`` - a list of raw (T, F) mel-amplitude arrays that the transform turns into the (B,1,frames,F) batch.
+        ``transform`` - a list of raw (T, F) mel-amplitude arrays that the transform turns into the (B,1,frames,F) batch (or, a
+        paired transform such as DeviceViewTransform, into the pair (x_teacher, x_student): the input of the batch is then that pair).
         targets_to_device=False leaves the targets on the host: the graphed steppers lay them out in ONE pinned blob and send one
         copy per step (sedt.TargetTables), which is cheaper than a copy per tensor here"""
         self.targets_to_device = targets_to_device
@@ -81,7 +82,7 @@ class DevicePrefetcher(object):
         torch.cuda.current_stream(self.dev).wait_stream(self.stream)
         inp, tgt, idx = self.next_input, self.next_target, self.next_index
         if inp is not None:
-            for t in ([inp.tensors] if isinstance(inp, NestedTensor) else [inp]):
+            for t in ([inp.tensors] if isinstance(inp, NestedTensor) else inp if isinstance(inp, (tuple, list)) else [inp]):
                 if torch.is_tensor(t):
                     t.record_stream(torch.cuda.current_stream(self.dev))
         self.preload()

@@ -88,3 +88,13 @@ def semi_view_transforms(T, device):
     mean, std = np.full(64, SEMI_SCALER[0]), np.full(64, SEMI_SCALER[1])
     return (DeviceBoxTransform(T, mean, std, time_mask=False, freq_mask=True, device=device),
             DeviceBoxTransform(T, mean, std, time_mask=True, freq_mask=True, device=device))
+
+
+def semi_pair_transform(T, device, snr_db=30.0, **kw):
+    """the ONE paired transform of the same recipe (utilities.transforms.DeviceViewTransform): raw clips go in once, (x_teacher,
+    x_student) come out, AugmentGaussianNoise(snr) for the student drawn on the device - the counterpart of synthetic_semi_raw's baked
+    noise + semi_view_transforms for a run on real data"""
+    import numpy as np
+    from .transforms import DeviceViewTransform
+    mean, std = np.full(64, SEMI_SCALER[0]), np.full(64, SEMI_SCALER[1])
+    return DeviceViewTransform(T, mean, std, noise_snr=snr_db, time_mask=True, freq_mask=True, device=device, **kw)

@@ -6,7 +6,8 @@ The reference runs them per clip in NumPy inside the DataLoader workers; at > 10
 Here a whole batch is ONE kernel launch (sedt_box_transform: a workgroup per clip, the clip stays in LDS between the passes).
 The RANDOM PARAMETERS are drawn on the host with np.random in exactly the order the reference's classes draw them
 (TimeMask.randomize_parameters :380-383, FreqMask :410-413, FreqShift :437-443), so a seeded run augments every clip the same
-way as the reference pipeline does."""
+way as the reference pipeline does.  DeviceViewTransform (sedt_box_transform_views) is the paired form for the mean-teacher
+recipe: both views from one raw clip, the student's Gaussian noise drawn inside the kernel."""
 import numpy as np
 import torch
 
@@ -139,6 +140,132 @@ class DeviceBoxTransform(object):
         L.check(L.load().sedt_box_transform(L.p(amp), stride, L.p(aug), L.p(self.mean), L.p(self.std), B, self.frames, self.F,
                                             int(self.apply_log), 1, 0.0, L.p(out), L.stream_ptr()), 'box_transform')
         return out
+
+
+# ------------------------------------------------------------------------------------------------ the two mean-teacher views
+_VAUG = np.dtype([('view', _AUG, (2,)), ('noise_on', np.int32), ('pad', np.int32)])      # SedtViewAug (include/sedt_hip.h)
+
+
+class DeviceViewTransform(DeviceBoxTransform):
+    """The noisy chain of the semi-supervised recipe (reference train_ss_sedt.py:87-97: get_transforms(noise_dict_params={"mean": 0.,
+    "snr": noise_snr}, freq_mask, freq_shift, time_mask)) for a whole batch in ONE launch (sedt_box_transform_views): a raw clip goes
+    in once and BOTH views come out - view 0 for the labelled pass and the teacher, view 1 (AugmentGaussianNoise with probability
+    ``noise_p``, BoxTransforms.py:121-180, then TimeMask, which skips view 0) for the student; FreqMask / FreqShift hit each view with
+    a draw of its own, as Transform._apply_transform (:19-35) does.
+
+    ``draw_batch`` consumes np.random in the reference's order, clip by clip: noise ``uniform(0, 1) < p``; (mode 'host' only, and
+    only when applied) the (T_raw, F) normals; TimeMask's three draws for view 1; FreqMask's three for view 0, then for view 1;
+    FreqShift's for view 0, then for view 1.
+
+    noise='host': the normals are drawn with np.random on the host and uploaded (the kernel's injected source), so a seeded run
+    reproduces a seeded reference pipeline draw for draw.  They are STANDARD normals - ``np.random.normal(0, std, shape)`` is
+    ``std * `` the same Gaussian stream, and the kernel does the scaling by the band std it computes itself - so the draw needs only
+    the clips' lengths, not their data.
+    noise='device' (the default): the normals never exist on the host; the kernel draws them from its counter-based stream
+    (``seed``, plus ``self.offset``, which every call advances by the elements of its batch).  The LATER host draws of a seeded
+    run then differ from the reference's: there the normals advance the same np.random generator the masks draw from.
+
+    The reference's other branch (``std=`` instead of ``snr=``, :172-173, which ignores the value and adds |N(0, 0.25^2)|) is not
+    part of the recipe and is not built: ``noise_snr=None`` raises."""
+
+    def __init__(self, frames, scaler_mean=None, scaler_std=None, noise_snr=30.0, noise_p=0.5, time_mask=False, freq_mask=False,
+                 freq_shift=False, noise='device', seed=0, noise_std=None, **kw):
+        if noise_snr is None or noise_std is not None:
+            raise ValueError("DeviceViewTransform builds the snr branch of AugmentGaussianNoise only: the recipe passes "
+                             "{'mean': 0., 'snr': noise_snr}; the std= branch (reference BoxTransforms.py:172-173) is not part of it")
+        if noise not in ('device', 'host'):
+            raise ValueError(f"noise must be 'device' or 'host', not {noise!r}")
+        super().__init__(frames, scaler_mean, scaler_std, time_mask=time_mask, freq_mask=freq_mask, freq_shift=freq_shift, **kw)
+        if self.F % 2:
+            raise ValueError('the normals come in pairs: n_mels must be even')
+        self.noise_snr, self.noise_p, self.noise, self.seed = float(noise_snr), float(noise_p), noise, int(seed) & 0xffffffff
+        self.seed_ptr = None              # optional device uint32 word added to the seed (a step that advances its own seed word)
+        self.offset = 0                   # stream position of the next call's first element (drawn mode)
+
+    def draw_batch(self, nraws):
+        """(records, normals): the _VAUG records of a batch and - mode 'host' - per clip the (T_raw, F) float64 standard normals of
+        its noise (None where the noise is not applied); normals is None in mode 'device'"""
+        u, nrm = np.random.uniform, np.random.normal
+        nf, nm = self.frames, self.F
+        rows, normals = [], ([] if self.noise == 'host' else None)
+        for n in nraws:
+            noise_on = int(u(0, 1) < self.noise_p)
+            if normals is not None:
+                normals.append(nrm(0.0, 1.0, (n, nm)) if noise_on else None)
+            tm_t = tm_t0 = 0
+            if self.time_mask:                                   # view 1 only
+                lo, hi, p = self.tm
+                apply = u(0, 1) < p
+                t = u(lo, hi)
+                t0 = u(0, 1 - t)
+                if apply:
+                    tm_t, tm_t0 = int(t * nf), int(t0 * nf)
+            fm = [(0, 0, 0), (0, 0, 0)]
+            if self.freq_mask:
+                lo, hi, p = self.fm
+                for k in (0, 1):
+                    apply = u(0, 1) < p
+                    f = u(lo, hi)
+                    f0 = u(0, 1 - f)
+                    if apply:
+                        fm[k] = (int(f * nm), int(f0 * nm), 1)
+            fs = [0, 0]
+            if self.freq_shift:
+                p, max_band, mean, std = self.fs
+                for k in (0, 1):
+                    apply = u(0, 1) < p
+                    s_ = int(nrm(mean, std))
+                    while abs(s_) > max_band:
+                        s_ = int(nrm(mean, std))
+                    if apply:
+                        fs[k] = s_
+            rows.append((n, 0, 0) + fm[0] + (fs[0], 0) + (n, tm_t, tm_t0) + fm[1] + (fs[1], 0) + (noise_on, 0))
+        return np.asarray(rows, np.int32).reshape(-1, 18).view(_VAUG).reshape(-1), normals
+
+    def __call__(self, clips, params=None, out=None, staging=None, normals=None):
+        """clips, staging: as DeviceBoxTransform.  params: optional _VAUG records (else drawn).  normals: the injected standard
+        normals, a list of per-clip (T_raw, F) arrays (None entries allowed) or a (B, stride, F) f32 device tensor; None with params
+        given, or in mode 'device', makes the kernel draw them.  out: optional pair of (B, 1, frames, F) f32 tensors.
+        Returns (x_teacher, x_student)."""
+        if torch.is_tensor(clips) and clips.is_cuda:
+            amp = clips.float().contiguous()
+            B, stride = amp.shape[0], amp.shape[1]
+            nraw = [stride] * B
+        else:
+            B = len(clips)
+            nraw = [int(c.shape[0]) for c in clips]
+            stride = max(nraw)
+            host = staging if staging is not None else torch.zeros((B, stride, self.F), dtype=torch.float32).pin_memory()
+            hv = host.numpy()
+            for i, c in enumerate(clips):
+                hv[i, :nraw[i]] = c.numpy() if torch.is_tensor(c) else c
+            amp = host.to(self.dev, non_blocking=True)
+        if params is None:
+            params, normals = self.draw_batch(nraw)
+        params = np.ascontiguousarray(params)
+        if params.dtype != _VAUG or len(params) != B or int(params['view']['nframes_raw'].max(initial=0)) > stride:
+            raise ValueError('params: one _VAUG record per clip, nframes_raw within the rows of the batch')
+        z = None
+        if torch.is_tensor(normals):
+            z = normals.to(self.dev).float().contiguous()
+            assert tuple(z.shape) == (B, stride, self.F), 'injected normals are laid out like the raw batch'
+        elif normals is not None:
+            zh = torch.zeros((B, stride, self.F), dtype=torch.float32).pin_memory()
+            for i, n in enumerate(normals):
+                if n is not None:
+                    zh.numpy()[i, :len(n)] = n
+            z = zh.to(self.dev, non_blocking=True)
+        aug = self._upload(params.view(np.uint8).reshape(-1))
+        if out is None:
+            out = (torch.empty((B, 1, self.frames, self.F), device=self.dev, dtype=torch.float32),
+                   torch.empty((B, 1, self.frames, self.F), device=self.dev, dtype=torch.float32))
+        x0, x1 = out
+        L.check(L.load().sedt_box_transform_views(L.p(amp), stride, L.p(aug), L.p(self.mean), L.p(self.std), B, self.frames, self.F,
+                                                  int(self.apply_log), 1, 0.0, self.noise_snr, L.p(z), self.seed, L.p(self.seed_ptr),
+                                                  self.offset, L.p(x0), L.p(x1), L.stream_ptr()), 'box_transform_views')
+        if z is None:
+            self.offset += B * stride * self.F
+        return x0, x1
 
 
 # ------------------------------------------------------------------------------------------------ SP-SEDT query patches
