@@ -78,7 +78,8 @@ int sedt_version(void);
  *   splitk > 1: partial sums go to slab[z][M][N] (f32) and the epilogue is skipped.
  *
  * epilogue, in order: v = acc*scale[n] + bias[n]; if(!act_post_res) v = act(v);
- *   dropout(v); v += res[(res_mod ? m % res_mod : m)*ldr + n]; if(act_post_res) v = act(v);
+ *   dropout(v); v += res[(res_mod ? m % res_mod : rmap ? coarse(m) : m)*ldr + n] (rmap: only where m lies on the coarse grid, see
+ *   SedtIgemm.rmap); if(act_post_res) v = act(v);
  *   v = mask[m*ldm+n] > 0 ? v : 0; v *= alpha; store as f32 (out_f32) or the compute dtype.
  * 1-bit ReLU masks (round 3): a backward pass needs only the SIGN of a saved post-ReLU activation.  mask_bits != 0: `mask` is a
  *   uint8 bit image - bit (n & 7) of mask[m*ldm + (n >> 3)], ldm in BYTES - instead of the activation itself (1/16 of the bytes of a
@@ -130,10 +131,19 @@ typedef struct SedtIgemm {
                              output, written by the epilogue - the GEMMs that consume this output then need no split pass */
   int32_t awrap;          /* bf16x3, trans == 0: the A rows hold [hi | lo] = 2 awrap channels while the contraction walks 3 awrap per pixel
                              (K = 3 awrap, a convolution: Ci = 3 awrap): the last third re-reads hi.  0 = off */
-  int32_t pad2_;
+  int32_t rmap;           /* != 0: the residual lives on a coarser grid (the input gradient of a stride-s 1x1 projection, held as the plain
+                             GEMM on the projection's OUTPUT grid).  Packed r_Hi | r_Wi << 12 | r_sh << 24 | r_sw << 28 (r_Hi, r_Wi <= 4095,
+                             1 <= r_sh, r_sw <= 15; SEDT_RMAP below): the output pixel - the GEMM row, or the omap-mapped row - is pixel
+                             (n, h, w) of an r_Hi x r_Wi image and takes res[((n * rH + h / r_sh) * rW + w / r_sw) * ldr + col], rH =
+                             (r_Hi - 1) / r_sh + 1, rW = (r_Wi - 1) / r_sw + 1, when r_sh divides h and r_sw divides w - and NO residual
+                             otherwise (it stores the bits of the same launch without `res`).  trans == 0, res_mod == 0, fewer than 2^24
+                             output pixels, a whole number of images; every kernel that reads `res` honours it, an entry point that
+                             cannot fails.  One packed word in the former padding: the struct keeps its size - ten of them travel in
+                             the kernel arguments of a grouped weight-gradient launch */
   const void* bfrag;      /* or null: the fragment-major image (sedt_pack_frag) of the WHOLE B operand [N][ldb] (trans == 0, bf16): kernels
                              that stream B from L2 into registers read it instead of B (developer build only so far) */
 } SedtIgemm;
+#define SEDT_RMAP(r_Hi, r_Wi, r_sh, r_sw) ((int32_t)((uint32_t)(r_Hi) | (uint32_t)(r_Wi) << 12 | (uint32_t)(r_sh) << 24 | (uint32_t)(r_sw) << 28))
 
 int sedt_igemm(const SedtIgemm* args, int dtype, void* stream);
 /* sizeof of an argument struct as THIS library was compiled (0 SedtIgemm, 1 SedtReduceJob, 2 SedtSplitJob, 3 SedtPrefetch, 4 SedtCriterion,

@@ -479,6 +479,21 @@ __global__ __launch_bounds__(256) void igemm_kernel(const SedtIgemm p, const int
   const uint32_t thresh = drop_threshold(p.drop_p);
   const float inv_keep = p.drop_p > 0.f ? 1.f / (1.f - p.drop_p) : 1.f;
   const T* resT = reinterpret_cast<const T*>(p.res);
+  // the residual's row for output row `row`; false = no residual there (SedtIgemm.rmap: the residual lives on a coarser grid and only
+  // the pixels on it take one).  Uniform branches: the common case pays no integer division.
+  auto res_row = [&](const int row, long& rr) -> bool {
+    rr = row;
+    if (p.res_mod > 0) {
+      rr = row % p.res_mod;
+    } else if (p.rmap) {
+      const unsigned rm = (unsigned)p.rmap;
+      const int rHi = rm & 0xfffu, rWi = (rm >> 12) & 0xfffu, rsh = (rm >> 24) & 15u, rsw = rm >> 28;
+      const int n = row / (rHi * rWi), rem = row - n * (rHi * rWi), h = rem / rWi, w = rem - h * rWi;
+      if (h % rsh != 0 || w % rsw != 0) return false;
+      rr = ((long)n * ((rHi - 1) / rsh + 1) + h / rsh) * ((rWi - 1) / rsw + 1) + w / rsw;
+    }
+    return true;
+  };
   const T* maskT = p.mask_bits ? nullptr : reinterpret_cast<const T*>(p.mask);
   const uint8_t* maskB = p.mask_bits ? reinterpret_cast<const uint8_t*>(p.mask) : nullptr;
   // one 32x32 accumulator tile; called with compile-time (i, j) so acc stays in registers
@@ -505,8 +520,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const SedtIgemm p, const int
           }
           if (p.drop_p > 0.f) v = drop_keep(seed, (uint64_t)row * (uint64_t)p.N + col, thresh) ? v * inv_keep : 0.f;
           if (resT) {
-            long rr = p.res_mod > 0 ? (row % p.res_mod) : row;
-            v += (float)resT[rr * p.ldr + col];
+            long rr;
+            if (res_row(row, rr)) v += (float)resT[rr * p.ldr + col];
           }
           if (p.act_post_res) {
             if (p.act == SEDT_ACT_RELU) v = fmaxf(v, 0.f);
@@ -535,8 +550,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const SedtIgemm p, const int
       }
       if (p.drop_p > 0.f) v = drop_keep(seed, (uint64_t)row * (uint64_t)p.N + col, thresh) ? v * inv_keep : 0.f;
       if (resT) {
-        long rr = p.res_mod > 0 ? (row % p.res_mod) : row;
-        v += (float)resT[rr * p.ldr + col];
+        long rr;
+        if (res_row(row, rr)) v += (float)resT[rr * p.ldr + col];
       }
       if (p.act_post_res) {
         if (p.act == SEDT_ACT_RELU) v = fmaxf(v, 0.f);
@@ -631,6 +646,27 @@ static int launch_typed(const SedtIgemm& p, hipStream_t st) {
 
 namespace sedt { int igemm_lds_try(const SedtIgemm& p, hipStream_t st); }   // igemm3.hip: the LDS-DMA GEMM family's dispatcher
 
+// SedtIgemm.rmap (the residual on a coarser grid) is honoured by every kernel behind sedt_igemm / sedt_igemm_group / sedt_igemm_co that reads
+// `res`; what they rely on is checked here, once, for all of them
+static int check_rmap(const SedtIgemm& p) {
+  if (!p.rmap) return 0;
+  const unsigned rm = (unsigned)p.rmap;
+  const long rHi = rm & 0xfffu, rWi = (rm >> 12) & 0xfffu, rsh = (rm >> 24) & 15u, rsw = rm >> 28;
+  SEDT_REQUIRE(p.res != nullptr && p.res_mod == 0 && !p.trans && p.splitk <= 1,
+               "igemm: rmap needs a residual, res_mod == 0, trans == 0 and no split-K (res %p res_mod %d trans %d splitk %d)", p.res, p.res_mod,
+               p.trans, p.splitk);
+  SEDT_REQUIRE(rHi >= 1 && rWi >= 1 && rsh >= 1 && rsw >= 1, "igemm: rmap %ld x %ld / (%ld, %ld): every part must be >= 1", rHi, rWi, rsh, rsw);
+  long pixels = p.M;
+  if (p.omap) {
+    SEDT_REQUIRE(p.conv && p.Ho > 0 && p.Wo > 0 && p.M % (p.Ho * p.Wo) == 0 && p.o_Hi == rHi && p.o_Wi == rWi,
+                 "igemm: rmap %ld x %ld over an omap image of %d x %d", rHi, rWi, p.o_Hi, p.o_Wi);
+    pixels = (long)(p.M / (p.Ho * p.Wo)) * p.o_Hi * p.o_Wi;
+  }
+  SEDT_REQUIRE(pixels % (rHi * rWi) == 0 && pixels < (1L << 24),
+               "igemm: rmap %ld x %ld needs a whole number of images and fewer than 2^24 output pixels (%ld)", rHi, rWi, pixels);
+  return 0;
+}
+
 static bool use_lds_family() {
   static int v = -1;
   if (v < 0) {
@@ -646,6 +682,7 @@ extern "C" int sedt_igemm(const SedtIgemm* args, int dtype, void* stream) {
   SEDT_REQUIRE(args->M > 0 && args->N > 0 && args->K > 0, "igemm: bad dims M=%d N=%d K=%d", args->M, args->N, args->K);
   SEDT_REQUIRE(args->A && args->B && (args->C || args->splitk > 1), "igemm: null operand");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int r = check_rmap(*args)) return r;
   if (dtype != SEDT_BF16)
     SEDT_REQUIRE(!args->omap && !args->btap_on && !args->f32ep && !args->awrap, "igemm: omap / btap / f32ep / awrap are features of the bf16 LDS-DMA kernels");
   if (dtype == SEDT_F32) {
@@ -706,6 +743,8 @@ int igemm3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st);
 
 extern "C" int sedt_igemm_group(const SedtIgemm* jobs, int njobs, int dtype, void* stream) {
   SEDT_REQUIRE(jobs && njobs >= 1, "igemm_group: bad arguments");
+  for (int i = 0; i < njobs; ++i)
+    if (int r = check_rmap(jobs[i])) return r;
   if (dtype == SEDT_BF16 && njobs >= 2) {
     const int r = sedt::igemm3_group_try(jobs, njobs, reinterpret_cast<hipStream_t>(stream));
     if (r >= 0) return r;
@@ -731,6 +770,7 @@ extern "C" int sedt_igemm_group_describe(const SedtIgemm* jobs, int njobs, int d
 
 extern "C" int sedt_wgrad_group(const SedtIgemm* jobs, int njobs, int dtype, void* stream) {
   SEDT_REQUIRE(jobs && njobs >= 1, "wgrad_group: bad arguments");
+  for (int i = 0; i < njobs; ++i) SEDT_REQUIRE(!jobs[i].rmap, "wgrad_group: a weight-gradient problem takes no residual map (job %d)", i);
   if (dtype == SEDT_BF16) {
     const int r = sedt::wgrad3_group_try(jobs, njobs, reinterpret_cast<hipStream_t>(stream));
     if (r >= 0) return r;
@@ -753,6 +793,7 @@ extern "C" int sedt_igemm_co(const SedtIgemm* main, const SedtIgemm* wjobs, int 
   using namespace sedt;
   SEDT_REQUIRE(main && (nw == 0 || wjobs) && taken, "igemm_co: bad arguments");
   *taken = 0;
+  for (int i = 0; i < nw; ++i) SEDT_REQUIRE(!wjobs[i].rmap, "igemm_co: a weight-gradient rider takes no residual map (job %d)", i);
   if (nw == 0) return sedt_igemm(main, dtype, stream);
   static int on = -1;
   if (on < 0) {

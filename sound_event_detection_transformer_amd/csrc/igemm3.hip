@@ -45,6 +45,34 @@ __device__ int g_ts_filter[3];      // (M, N, K) of the only problem that record
 #define SEDT_TS(i_, v_) do {} while (0)
 #endif
 
+// SedtIgemm.rmap: the coarse-grid row that output pixel `orow` reads its residual from, or -1 when the pixel lies off that grid.  Out of
+// line on purpose: inlined into the three places that read `res`, its temporaries cost the 64x128 ping-pong kernel 17 VGPRs and with them
+// its second workgroup per CU.  The two divisions left in the power-of-two stride case go through a float reciprocal with an integer
+// correction (exact below 2^24 pixels, which sedt_igemm requires; tests/test_proj_compact_cpu.py walks the same arithmetic): this runs
+// once per 8-column chunk of problems whose whole workgroup lives a few microseconds.
+__device__ __noinline__ long rmap_row(const int orow, const unsigned rm) {
+  const int rHi = rm & 0xfffu, rWi = (rm >> 12) & 0xfffu, rsh = (rm >> 24) & 15u, rsw = rm >> 28;
+  auto divmod = [](const int a, const int b, int& q, int& r) {
+    q = (int)((float)a * (1.f / (float)b));
+    r = a - q * b;
+    if (r < 0) { --q; r += b; }
+    if (r >= b) { ++q; r -= b; }
+  };
+  int n, rem, h, w;
+  divmod(orow, rHi * rWi, n, rem);
+  divmod(rem, rWi, h, w);
+  if (((rsh & (rsh - 1)) | (rsw & (rsw - 1))) == 0) {          // strides 1, 2, 4, 8 (uniform branch): shifts
+    const int lh = __builtin_ctz(rsh), lw = __builtin_ctz(rsw);
+    if (((h & (rsh - 1)) | (w & (rsw - 1))) != 0) return -1;
+    return ((long)n * (((rHi - 1) >> lh) + 1) + (h >> lh)) * (((rWi - 1) >> lw) + 1) + (w >> lw);
+  }
+  int hc, hr, wc, wr;
+  divmod(h, rsh, hc, hr);
+  divmod(w, rsw, wc, wr);
+  if (hr != 0 || wr != 0) return -1;
+  return ((long)n * ((rHi - 1) / rsh + 1) + hc) * ((rWi - 1) / rsw + 1) + wc;
+}
+
 // S = ring depth (stages); bx = index of this workgroup among the problem's tiles; NW = waves per workgroup: 4, or 8 = two
 // groups of four that each own the full output tile but only half of the k16 steps of every K tile (their accumulators are
 // added through LDS in the epilogue).  The 8-wave form gives a 128x128 tile - 64 flop per byte fetched from L2 instead of
@@ -167,6 +195,20 @@ __device__ __forceinline__ void igemm3_impl(const SedtIgemm& p, const unsigned a
     const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
     return ((long)n * p.o_Hi + ho * p.o_sh + p.o_h0) * p.o_Wi + wo * p.o_sw + p.o_w0;
   };
+  // the residual's row for output pixel `orow`; false = this pixel takes no residual.  res_mod: rows repeat.  rmap (the residual lives on a
+  // coarser grid, see the header): only the pixels on that grid take one (rmap_row).  Both are uniform branches: the common case pays no
+  // integer division.
+  const uint4 NEG_ZERO8 = make_uint4(0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u);       // eight bf16 -0
+  auto res_row = [&](const long orow, long& rrow) -> bool {
+    rrow = orow;
+    if (p.res_mod > 0) {
+      rrow = orow % p.res_mod;
+    } else if (p.rmap) {
+      rrow = rmap_row((int)orow, (unsigned)p.rmap);
+      if (rrow < 0) return false;
+    }
+    return true;
+  };
   if constexpr (!LATE) {
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
@@ -175,9 +217,10 @@ __device__ __forceinline__ void igemm3_impl(const SedtIgemm& p, const unsigned a
     if (row < p.M && col < p.N && (!PARTIAL || u < BM * CPR)) {
       const long orow = out_row(row);
       if (resT) {
-        long rrow = orow;
-        if (p.res_mod > 0) rrow = orow % p.res_mod;          // uniform branch: the common case pays no integer division
-        res_pf[c] = *reinterpret_cast<const bf16x8*>(resT + rrow * p.ldr + col);
+        // (a pixel off the residual's grid holds -0: v + -0 is v for every v, -0 and +0 included - the bits of the launch without a residual)
+        long rrow;
+        if (res_row(orow, rrow)) res_pf[c] = *reinterpret_cast<const bf16x8*>(resT + rrow * p.ldr + col);
+        else res_pf[c] = __builtin_bit_cast(bf16x8, NEG_ZERO8);
       }
       if (maskT) mask_pf[c] = *reinterpret_cast<const bf16x8*>(maskT + orow * p.ldm + col);
       if (maskB) mbit_pf[c] = maskB[orow * p.ldm + (col >> 3)];
@@ -580,24 +623,27 @@ __device__ __forceinline__ void igemm3_impl(const SedtIgemm& p, const unsigned a
         v[2 * q + 1] = (h >> 16) >= thresh ? v[2 * q + 1] * inv_keep : 0.f;
       }
     }
+    // (a pixel off the residual's grid: the prefetched chunk holds -0, the late forms skip the addition - either way v keeps its bits)
     if (resT) {
-      bf16x8 rv;
       if constexpr (LATE) {
-        long rrow = orow;
-        if (p.res_mod > 0) rrow = orow % p.res_mod;
-        rv = *reinterpret_cast<const bf16x8*>(resT + rrow * p.ldr + col);
-      } else {
-        rv = res_pf[c];
-      }
+        long rrow;
+        if (res_row(orow, rrow)) {
+          const bf16x8 rv = *reinterpret_cast<const bf16x8*>(resT + rrow * p.ldr + col);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
+          for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += (float)res_pf[c][e];
+      }
     }
     if (resF) {
-      long rrow = orow;
-      if (p.res_mod > 0) rrow = orow % p.res_mod;
-      const float4 r0 = *reinterpret_cast<const float4*>(resF + rrow * p.ldr + col);
-      const float4 r1 = *reinterpret_cast<const float4*>(resF + rrow * p.ldr + col + 4);
-      v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
+      long rrow;
+      if (res_row(orow, rrow)) {
+        const float4 r0 = *reinterpret_cast<const float4*>(resF + rrow * p.ldr + col);
+        const float4 r1 = *reinterpret_cast<const float4*>(resF + rrow * p.ldr + col + 4);
+        v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
+      }
     }
     if (relu_post) {
 #pragma unroll

@@ -1049,13 +1049,14 @@ class StageFn(Function):
             if blk.ds and t[15].requires_grad:
                 grads[base + 15] = ops.wgrad(dt, gp, r['x'], B, r['gd'], rowscale=r['sd'], batch=rb, param=t[15])
             if want_gx:
-                side = ops.conv_dgrad(dt, gp, B, r['gd'], r['wdb']) if blk.ds else gp
+                # (a stride-2 projection: its input gradient stays on the projection's output grid, ops.proj_dgrad)
+                side, ep_side = ops.proj_dgrad(dt, gp, B, r['gd'], r['wdb']) if blk.ds else (gp, dict(ldr=gp.stride(0)))
                 mask_x = (not first) or meta['mask_input']
                 if mask_x and r.get('xbits') is not None:
                     ep = dict(mask=r['xbits'], ldm=r['xbits'].stride(0), mask_bits=True)
                 else:
                     ep = dict(mask=r['x'], ldm=r['x'].stride(0)) if mask_x else {}
-                gp = ops.conv_dgrad(dt, ga, B, r['g1'], w1b, res=side, ldr=side.stride(0), **ep)
+                gp = ops.conv_dgrad(dt, ga, B, r['g1'], w1b, res=side, **ep_side, **ep)
             else:
                 gp = None
         # the reduce launch that closes this stage touches the weights the stage BELOW streams first in its backward

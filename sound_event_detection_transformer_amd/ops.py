@@ -57,8 +57,9 @@ def _dev_check(*ts):
 
 def igemm_args(M, N, K, A, lda, B, ldb, Cout, ldc, *, trans=0, conv=None, transposed=0, out_f32=0, scale=None,
                bias=None, res=None, ldr=0, res_mod=0, mask=None, ldm=0, act=ACT_NONE, act_post_res=0, alpha=1.0, drop_p=0.0,
-               seed=0, seed_ptr=None, splitk=1, slab=None, tile=(0, 0), colsum_out=None, mask_bits=False, bits_out=None):
-    """the SedtIgemm argument block of one implicit GEMM; ``conv`` = (Hi, Wi, Ci, Ho, Wo, KH, KW, sh, sw, ph, pw, dh, dw)"""
+               seed=0, seed_ptr=None, splitk=1, slab=None, tile=(0, 0), colsum_out=None, mask_bits=False, bits_out=None, res_map=None):
+    """the SedtIgemm argument block of one implicit GEMM; ``conv`` = (Hi, Wi, Ci, Ho, Wo, KH, KW, sh, sw, ph, pw, dh, dw);
+    ``res_map`` = (r_Hi, r_Wi, r_sh, r_sw): ``res`` lives on the coarse grid of an r_Hi x r_Wi image (SedtIgemm.rmap)"""
     _dev_check(A, B, Cout)
     a = L.SedtIgemm()
     a.M, a.N, a.K = M, N, K
@@ -76,6 +77,10 @@ def igemm_args(M, N, K, A, lda, B, ldb, Cout, ldc, *, trans=0, conv=None, transp
     a.bias = bias.data_ptr() if bias is not None else None
     a.res = res.data_ptr() if res is not None else None
     a.ldr, a.res_mod = ldr, res_mod
+    if res_map is not None:
+        r_Hi, r_Wi, r_sh, r_sw = res_map
+        assert res is not None and not res_mod and 1 <= r_Hi < 4096 and 1 <= r_Wi < 4096 and 1 <= r_sh < 16 and 1 <= r_sw < 16, res_map
+        a.rmap = C.c_int32(r_Hi | r_Wi << 12 | r_sh << 24 | r_sw << 28).value
     a.mask = mask.data_ptr() if mask is not None else None
     a.ldm = ldm
     a.act, a.act_post_res, a.alpha = act, act_post_res, alpha
@@ -642,6 +647,8 @@ def conv_dgrad(dtype, dy, B, g, wb, out=None, **ep):
     if _conv3_c64_ok(dtype, dy, g, ep, out) and 'scale' not in ep and 'bias' not in ep:
         return _conv3_c64(dy, B, g, wb, 1, out, ep)       # the input gradient of a stride-1 3x3 conv is the same conv, taps flipped
     conv = None if g.plain else _geom_tuple(g, transposed=True)
+    if L.LAUNCH_LOG is not None and not g.plain:          # (a transposed gather on the general path: which geometry)
+        L.LAUNCH_LOG['conv_dgrad_gather:k%ds%d' % (g.KH, g.sh)] += 1
     global PROFILE_HINT
     if PROFILE is not None and _conv3_c64_ok(dtype, dy, g, ep, out, True) and 'scale' not in ep and 'bias' not in ep:
         PROFILE_HINT = 'conv3x3_c64_kernel'
@@ -654,6 +661,33 @@ def conv_dgrad(dtype, dy, B, g, wb, out=None, **ep):
           transposed=0 if g.plain else 1, **ep)
     PROFILE_HINT = None
     return out
+
+
+# The input gradient of a stride-s 1x1 projection (pad 0: the skip path of layer2's / layer3's block 0) is non-zero only on the pixels the
+# projection read - every s-th row and column, a quarter of the map at s = 2 - and there it is the plain GEMM dY W over the projection's
+# OUTPUT grid.  proj_dgrad computes just that, [B Ho Wo, Ci]; the one consumer - conv1's input gradient, which takes it as its residual -
+# reads it through SedtIgemm.rmap.  The dense form (a transposed gather over the input grid: three of four GEMM rows multiply zeros, three
+# quarters of the result are zeros written to HBM and read back) stays behind the developer attribute for same-build A/Bs and as the
+# reference path of tests/test_proj_compact_gpu.py.
+PROJ_COMPACT = _dev_env('SEDT_PROJ_COMPACT', '1') != '0'
+
+
+def proj_compact_ok(g):
+    return PROJ_COMPACT and g.KH == 1 and g.KW == 1 and (g.sh > 1 or g.sw > 1) and g.ph == 0 and g.pw == 0 and g.dh == 1 and g.dw == 1
+
+
+def proj_dgrad(dtype, dy, B, g, wb):
+    """(side, extra epilogue arguments of the GEMM that takes it as ``res``): the input gradient of the 1x1 projection ``g`` from
+    dy [B*Ho*Wo, Co] and wb, the packed dgrad operand [Ci][1][Co]"""
+    if not proj_compact_ok(g):
+        side = conv_dgrad(dtype, dy, B, g, wb)
+        return side, dict(ldr=side.stride(0))
+    M = B * g.Ho * g.Wo
+    side = torch.empty((M, g.Ci), device=dy.device, dtype=TORCH_DTYPE[dtype])
+    if L.LAUNCH_LOG is not None:
+        L.LAUNCH_LOG['proj_dgrad:%dx%dx%d' % (M, g.Ci, g.Co)] += 1
+    igemm(dtype, M, g.Ci, g.Co, dy, dy.stride(0), wb, g.Co, side, side.stride(0))
+    return side, dict(ldr=side.stride(0), res_map=(g.Hi, g.Wi, g.sh, g.sw))
 
 
 def _fused_bias_ok(dtype, dy, x, g):
