@@ -841,6 +841,23 @@ typedef struct {
 int sedt_box_transform_views(const float* amp, int64_t raw_stride, const void* aug, const double* mean, const double* stdv, int B,
                              int frames, int F, int apply_log, int fill_mean, float fill_const, float snr_db, const float* z,
                              uint32_t seed, const uint32_t* seed_ptr, uint64_t offset, float* out0, float* out1, void* stream);
+/* sedt_scaler_update: one batch of the dataset Scaler's fit (utilities/Scaler.py:37-100, means / calculate_scaler over the data set
+ * that passes through get_transforms(frames): ApplyLog -> PadOrTrunc -> ToTensor) on the device, so that the statistics are those of
+ * the very features sedt_box_transform later normalises: pass 1 of that kernel (dB, the clip maximum over ALL nframes_raw[b] raw rows,
+ * the 80 dB floor on the kept real rows; apply_log = 0 skips it) and nothing after it - no mask, no shift, no normalisation.
+ *   stage 1 (one workgroup of 1024 per clip, the clip in LDS): clip_stats[b][0][c] = mean over the `frames` rows of v widened to
+ *     float64, clip_stats[b][1][c] = mean of fl32(v * v) widened (the reference squares the f32 array, :57, before the float64 mean).
+ *     Rows >= min(nframes_raw[b], frames) are PadOrTrunc's zeros: they add nothing and count in the divisor.  Thread (g, c) adds rows
+ *     g, g + G, ... of band c (G = 1024 / F), then the G partials of a band are added in index order.
+ *   stage 2 (a second launch of one workgroup, behind stage 1 on the same stream): acc[k][c] += clip_stats[b][k][c] for
+ *     b = 0 .. B-1 in that order (the reference's `self.mean_ += mean(sample)`, :67-75), count[0] += B.
+ * No floating-point atomics: acc is a function of the sequence of clips alone, however it is cut into batches.  The caller zeroes
+ * acc and count before the first batch and divides by count at the end (mean_ = acc[0] / count, mean_of_square_ = acc[1] / count).
+ * amp [B][raw_stride][F] f32 (rows >= nframes_raw[b] ignored; nframes_raw is clamped to raw_stride), nframes_raw int32 [B],
+ * clip_stats float64 [B][2][F] scratch, acc float64 [2][F], count int64 [1], all device memory.
+ * frames * F * 4 + 2 * G * F * 8 + 64 bytes <= 160 KB of LDS, F <= 1024; otherwise an error. */
+int sedt_scaler_update(const float* amp, int64_t raw_stride, const int32_t* nframes_raw, int B, int frames, int F, int apply_log,
+                       double* clip_stats, double* acc, int64_t* count, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

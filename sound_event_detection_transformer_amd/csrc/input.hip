@@ -184,6 +184,62 @@ __global__ __launch_bounds__(1024) void box_transform_views_kernel(const float* 
   box_transform_tail(mx, a, mean, stdv, frames, F, apply_log, fill_mean, fill_const, (k ? out1 : out0) + (long)b * frames * F, clip, red);
 }
 
+// ---- the dataset Scaler (reference utilities/Scaler.py:37-100: means / calculate_scaler over get_transforms(frames): ApplyLog ->
+// PadOrTrunc -> ToTensor).  Stage 1, one workgroup per clip: pass 1 of box_transform_kernel word for word (dB, clip maximum over ALL raw
+// rows, the kept rows in LDS), the 80 dB floor on the kept real rows, then per band the float64 sum of v and of fl32(v * v) - the
+// reference squares the f32 array (Scaler.py:57) before np.mean(..., dtype=float64) widens it.  PadOrTrunc's zero rows add nothing and
+// are never written; they count in the divisor `frames`.  Summation order: thread (g, c) adds rows g, g + G, ... of band c (G = 1024 / F),
+// then the G partials of a band are added in index order.  No floating-point atomics: the result is a function of the clip alone.
+__global__ __launch_bounds__(1024) void scaler_clip_stats_kernel(const float* __restrict__ amp, long raw_stride,
+                                                                 const int32_t* __restrict__ nframes_raw, int frames, int F, int apply_log,
+                                                                 double* __restrict__ clip_stats) {
+  extern __shared__ double lds_d[];
+  const int G = 1024 / F;
+  double* part = lds_d;                                                    // [2][G][F]
+  float* clip = reinterpret_cast<float*>(lds_d + 2L * G * F);             // [frames][F]
+  float* red = clip + (long)frames * F;                                    // [16]
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int nraw = (int)min((long)max(nframes_raw[b], 0), raw_stride);     // never past the rows the batch holds
+  const float* src = amp + (long)b * raw_stride * F;
+  float mx = -INFINITY;
+  for (long i = t; i < (long)nraw * F; i += 1024) mx = fmaxf(mx, to_db_keep(src[i], i, apply_log, (long)frames * F, clip));
+  mx = block_max(mx, red);                                                 // (its barriers also publish the clip)
+  const float floor_db = mx - 80.f;               // top_db = 80
+  const int keep = min(nraw, frames);
+  const int g = t / F, c = t - g * F;
+  if (g < G) {
+    double s = 0.0, q = 0.0;
+    for (int r = g; r < keep; r += G) {
+      float v = clip[(long)r * F + c];
+      if (apply_log) v = fmaxf(v, floor_db);
+      const float vv = v * v;                     // rounded to f32 like the reference's array ** 2
+      s += (double)v;
+      q += (double)vv;
+    }
+    part[(long)g * F + c] = s;
+    part[((long)G + g) * F + c] = q;
+  }
+  __syncthreads();
+  for (int i = t; i < 2 * F; i += 1024) {
+    const int k = i / F, cc = i - k * F;
+    double s = 0.0;
+    for (int p = 0; p < G; ++p) s += part[((long)k * G + p) * F + cc];     // fixed order
+    clip_stats[(long)b * 2 * F + i] = s / (double)frames;
+  }
+}
+
+// Stage 2, one workgroup: the reference's `self.mean_ += mean(sample)` loop (Scaler.py:67-75) - element i of acc [2][F] takes the
+// clips' values in clip order, so a data set gives the same bits however it is cut into batches.
+__global__ __launch_bounds__(256) void scaler_accumulate_kernel(const double* __restrict__ clip_stats, int B, int n, double* __restrict__ acc,
+                                                                int64_t* __restrict__ count) {
+  for (int i = threadIdx.x; i < n; i += 256) {
+    double a = acc[i];
+    for (int b = 0; b < B; ++b) a += clip_stats[(long)b * n + i];
+    acc[i] = a;
+  }
+  if (threadIdx.x == 0) count[0] += B;
+}
+
 struct MixJob {                // mirrors utilities/mixup.py (4 x int32 + 1 float per output clip)
   int32_t src1, src2;          // rows of x1 / x2
   int32_t mode;                // 0: lam * x1[src1] + (1 - lam) * x2[src2], 1: x1[src1], 2: x2[src2]
@@ -438,6 +494,26 @@ extern "C" int sedt_box_transform_views(const float* amp, int64_t raw_stride, co
                      reinterpret_cast<const ViewAug*>(aug), mean, stdv, frames, F, apply_log, fill_mean, fill_const,
                      (float)pow(10.0, -(double)snr_db / 10.0), z, seed, seed_ptr, offset, out0, out1);
   return check_launch("box_transform_views");
+}
+
+extern "C" int sedt_scaler_update(const float* amp, int64_t raw_stride, const int32_t* nframes_raw, int B, int frames, int F, int apply_log,
+                                  double* clip_stats, double* acc, int64_t* count, void* stream) {
+  using namespace sedt;
+  SEDT_REQUIRE(amp && nframes_raw && clip_stats && acc && count, "scaler_update: null pointer");
+  SEDT_REQUIRE(B >= 0 && frames >= 1 && F >= 1 && F <= 1024 && raw_stride >= 1, "scaler_update: B=%d frames=%d F=%d", B, frames, F);
+  const size_t lds = 2 * (size_t)(1024 / F) * F * sizeof(double) + ((size_t)frames * F + 16) * sizeof(float);
+  SEDT_REQUIRE(lds <= 160 * 1024, "scaler_update: a clip of %d x %d f32 and its band partials do not fit the 160 KB LDS", frames, F);
+  if (B == 0) return 0;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scaler_clip_stats_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(scaler_clip_stats_kernel, dim3(B), dim3(1024), lds, s, amp, (long)raw_stride, nframes_raw, frames, F, apply_log,
+                     clip_stats);
+  hipLaunchKernelGGL(scaler_accumulate_kernel, dim3(1), dim3(256), 0, s, clip_stats, B, 2 * F, acc, count);
+  return check_launch("scaler_update");
 }
 
 extern "C" int sedt_mixup(const float* x1, const float* x2, const void* jobs, int n_out, int64_t clip_elems, float* out, void* stream) {

@@ -208,6 +208,7 @@ SIGNATURES = {
     'sedt_pool_at_bwd': (_i, [C.POINTER(SedtPoolAt), _vp, _vp, _vp, _vp, _vp]),
     'sedt_box_transform': (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     'sedt_box_transform_views': (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _u32, _vp, C.c_uint64, _vp, _vp, _vp]),
+    'sedt_scaler_update': (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_query_patches': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),

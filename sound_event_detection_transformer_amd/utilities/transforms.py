@@ -17,14 +17,64 @@ _AUG = np.dtype([('nframes_raw', np.int32), ('tm_t', np.int32), ('tm_t0', np.int
                  ('fm_on', np.int32), ('fs_shift', np.int32), ('pad', np.int32)])
 
 
+def stage_clips(clips, n_mels, dev, staging=None):
+    """a batch of raw clips on the device, for DeviceBoxTransform, DeviceViewTransform and utilities.scaler.Scaler alike.  clips: a
+    (B, T_raw, n_mels) tensor already on the device, or a list of ragged (T_raw, n_mels) arrays / tensors, which go through a pinned
+    buffer (``staging``, or a fresh one).  Returns (amp (B, stride, n_mels) f32 on the device, B, stride, rows per clip)."""
+    if torch.is_tensor(clips) and clips.is_cuda:
+        amp = clips.float().contiguous()
+        B, stride = amp.shape[0], amp.shape[1]
+        return amp, B, stride, [stride] * B
+    B = len(clips)
+    nraw = [int(c.shape[0]) for c in clips]
+    stride = max(nraw)
+    host = staging if staging is not None else torch.zeros((B, stride, n_mels), dtype=torch.float32).pin_memory()
+    hv = host.numpy()
+    for i, c in enumerate(clips):                       # plain memcpys into the pinned buffer (rows >= nraw[i] are never read)
+        hv[i, :nraw[i]] = c.numpy() if torch.is_tensor(c) else c
+    return host.to(dev, non_blocking=True), B, stride, nraw
+
+
+class PinnedRing(object):
+    """small per-batch records (bytes) through a ring of PINNED staging buffers: a copy from pageable memory blocks the host until
+    everything queued before it has run - the host would lose its run-ahead over the GPU on every batch (measured on the C5
+    step: 8.25 -> 8.65 ms)"""
+
+    def __init__(self, dev):
+        self.dev, self.pin, self.ev, self.devbuf, self.k = dev, [], [], [], 0
+
+    def upload(self, raw):
+        n = raw.size
+        if not self.pin or self.pin[0].numel() < n:
+            self.pin = [torch.zeros(max(n, 4096), dtype=torch.uint8).pin_memory() for _ in range(4)]
+            self.devbuf = [torch.zeros(max(n, 4096), dtype=torch.uint8, device=self.dev) for _ in range(4)]
+            self.ev = [None] * 4
+        k = self.k
+        self.k = (k + 1) % 4
+        if self.ev[k] is not None:
+            self.ev[k].synchronize()
+        self.pin[k].numpy()[:n] = raw
+        self.devbuf[k][:n].copy_(self.pin[k][:n], non_blocking=True)
+        self.ev[k] = torch.cuda.Event()
+        self.ev[k].record()
+        return self.devbuf[k]
+
+
 class DeviceBoxTransform(object):
     """frames: fixed number of frames (config.max_frames); scaler_mean / scaler_std: per-mel float64 vectors of the dataset
     Scaler (None: no normalisation); time_mask / freq_mask / freq_shift: enable the augmentations (their constructor
     defaults are the reference's: TimeMask(0.0, 0.1, p=0.2), FreqMask(0.03, 0.4, fill "mean", p=0.5), FreqShift(p=0.5,
-    max_band=4, std=2)); apply_log=False takes inputs that are already in dB."""
+    max_band=4, std=2)); apply_log=False takes inputs that are already in dB; scaler: a fitted or loaded utilities.scaler.Scaler,
+    equal to passing its mean_ and std_ as scaler_mean / scaler_std (one form or the other)."""
 
     def __init__(self, frames, scaler_mean=None, scaler_std=None, time_mask=False, freq_mask=False, freq_shift=False,
-                 apply_log=True, n_mels=64, device='cuda', tm=(0.0, 0.1, 0.2), fm=(0.03, 0.4, 0.5), fs=(0.5, 4, 0.0, 2.0)):
+                 apply_log=True, n_mels=64, device='cuda', tm=(0.0, 0.1, 0.2), fm=(0.03, 0.4, 0.5), fs=(0.5, 4, 0.0, 2.0), scaler=None):
+        if scaler is not None:
+            if scaler_mean is not None or scaler_std is not None:
+                raise ValueError('pass the statistics either as scaler= or as scaler_mean= / scaler_std=, not both')
+            if getattr(scaler, 'mean_', None) is None or getattr(scaler, 'std_', None) is None:
+                raise ValueError('scaler= needs a fitted or loaded Scaler (mean_ and std_ are not set)')
+            scaler_mean, scaler_std = scaler.mean_, scaler.std_
         self.frames, self.F, self.dev = frames, n_mels, torch.device(device)
         self.time_mask, self.freq_mask, self.freq_shift, self.apply_log = time_mask, freq_mask, freq_shift, apply_log
         self.tm, self.fm, self.fs = tm, fm, fs
@@ -34,24 +84,11 @@ class DeviceBoxTransform(object):
             self.std = torch.as_tensor(np.asarray(scaler_std, np.float64)).to(self.dev)
 
     def _upload(self, raw):
-        """the per-clip parameter records through a ring of PINNED staging buffers: a copy from pageable memory blocks the host until
-        everything queued before it has run - the host would lose its run-ahead over the GPU on every batch (measured on the C5
-        step: 8.25 -> 8.65 ms)"""
-        n = raw.size
-        ring = self.__dict__.setdefault('_ring', {'pin': [], 'ev': [], 'dev': [], 'k': 0})
-        if not ring['pin'] or ring['pin'][0].numel() < n:
-            ring['pin'] = [torch.zeros(max(n, 4096), dtype=torch.uint8).pin_memory() for _ in range(4)]
-            ring['dev'] = [torch.zeros(max(n, 4096), dtype=torch.uint8, device=self.dev) for _ in range(4)]
-            ring['ev'] = [None] * 4
-        k = ring['k']
-        ring['k'] = (k + 1) % 4
-        if ring['ev'][k] is not None:
-            ring['ev'][k].synchronize()
-        ring['pin'][k].numpy()[:n] = raw
-        ring['dev'][k][:n].copy_(ring['pin'][k][:n], non_blocking=True)
-        ring['ev'][k] = torch.cuda.Event()
-        ring['ev'][k].record()
-        return ring['dev'][k]
+        """the per-clip parameter records through this transform's ring of pinned staging buffers (PinnedRing)"""
+        ring = self.__dict__.get('_ring')
+        if ring is None:
+            ring = self._ring = PinnedRing(self.dev)
+        return ring.upload(raw)
 
     def draw(self, nframes_raw):
         """one record of augmentation parameters for a clip, consuming np.random like the reference's transform objects"""
@@ -118,19 +155,7 @@ class DeviceBoxTransform(object):
     def __call__(self, clips, params=None, out=None, staging=None):
         """clips: list of (T_raw, n_mels) float arrays / tensors (mel amplitudes), or a (B, T_raw, n_mels) tensor already on
         the device.  params: optional structured array of _AUG records (else drawn).  Returns (B, 1, frames, n_mels) f32."""
-        if torch.is_tensor(clips) and clips.is_cuda:
-            amp = clips.float().contiguous()
-            B, stride = amp.shape[0], amp.shape[1]
-            nraw = [stride] * B
-        else:
-            B = len(clips)
-            nraw = [int(c.shape[0]) for c in clips]
-            stride = max(nraw)
-            host = staging if staging is not None else torch.zeros((B, stride, self.F), dtype=torch.float32).pin_memory()
-            hv = host.numpy()
-            for i, c in enumerate(clips):                       # plain memcpys into the pinned buffer (rows >= nraw[i] are never read)
-                hv[i, :nraw[i]] = c.numpy() if torch.is_tensor(c) else c
-            amp = host.to(self.dev, non_blocking=True)
+        amp, B, stride, nraw = stage_clips(clips, self.F, self.dev, staging)
         if params is None:
             params = self.draw_batch(nraw)
         params = np.ascontiguousarray(params)
@@ -227,19 +252,7 @@ class DeviceViewTransform(DeviceBoxTransform):
         normals, a list of per-clip (T_raw, F) arrays (None entries allowed) or a (B, stride, F) f32 device tensor; None with params
         given, or in mode 'device', makes the kernel draw them.  out: optional pair of (B, 1, frames, F) f32 tensors.
         Returns (x_teacher, x_student)."""
-        if torch.is_tensor(clips) and clips.is_cuda:
-            amp = clips.float().contiguous()
-            B, stride = amp.shape[0], amp.shape[1]
-            nraw = [stride] * B
-        else:
-            B = len(clips)
-            nraw = [int(c.shape[0]) for c in clips]
-            stride = max(nraw)
-            host = staging if staging is not None else torch.zeros((B, stride, self.F), dtype=torch.float32).pin_memory()
-            hv = host.numpy()
-            for i, c in enumerate(clips):
-                hv[i, :nraw[i]] = c.numpy() if torch.is_tensor(c) else c
-            amp = host.to(self.dev, non_blocking=True)
+        amp, B, stride, nraw = stage_clips(clips, self.F, self.dev, staging)
         if params is None:
             params, normals = self.draw_batch(nraw)
         params = np.ascontiguousarray(params)
