@@ -286,8 +286,10 @@ int sedt_gelu_bwd(const void* g, const void* h, void* out, int64_t n, float p, u
 /* y = g * s * (1 - s) (sigmoid backward), all f32 */
 int sedt_sigmoid_grad(const float* g, const float* s, float* out, int64_t n, void* stream);
 
-/* ------------------------------------------------------------------ LayerNorm (width D = 256)
- * y = (x-mean)*rstd*gamma+beta ; y2 = y + add (optional) ; saves mean/rstd.  eps = 1e-5. */
+/* ------------------------------------------------------------------ LayerNorm (width D = 256 or 512)
+ * y = (x-mean)*rstd*gamma+beta ; y2 = y + add (optional) ; saves mean/rstd.  eps = 1e-5.
+ * Rows are contiguous (D elements apart) and every lane moves its D / 64 features as one vector: the row tensors (x, add, y, y2; dy, dy2,
+ * dres, dres2, dx, dx_drop) must be aligned to D / 64 elements of the dtype, gamma and beta to D / 64 floats - otherwise an error, no launch. */
 int sedt_layernorm_fwd(const void* x, const float* gamma, const float* beta, const void* add, void* y, void* y2,
                        float* mean, float* rstd, int rows, int D, int dtype, void* stream);
 /* dx = dres + LN'(dy (+dy2)); dgamma/dbeta: f32[D] (deterministic two-stage reduction) */
@@ -320,6 +322,16 @@ int sedt_attention_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, c
                        const uint8_t* kpm, const float* amask, void* dq, int64_t lddq, void* dk, int64_t lddk,
                        void* dv, int64_t lddv, int B, int H, int Lq, int Lk, float drop_p, uint32_t seed,
                        const uint32_t* seed_ptr, int dtype, void* stream);
+/* measurement and test aid, in the manner of sedt_igemm_describe: the name of the kernel instance - as rocprofv3 prints it, e.g.
+ * "attn_bwd_mfma_kernel<2, 3, true>", "attn_f32_fwd_kernel<4, false, true>", "attn_fwd_kernel<__bf16>" - that sedt_attention_fwd
+ * (backward = 0; dout, dq, dk, dv and their strides are ignored) or sedt_attention_bwd (backward = 1) launches for these pointers,
+ * strides, lengths, dropout probability and dtype, with an additive mask present or not.  The entry point itself runs in describe
+ * mode, so the answer cannot differ from the launch; nothing is dereferenced (pointers are tested for null and alignment only) and
+ * nothing is launched.  A call the entry point refuses gives "" and a non-zero return (sedt_last_error has the reason). */
+int sedt_attention_describe(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
+                            int64_t ldo, const void* dout, int64_t lddo, const void* dq, int64_t lddq, const void* dk,
+                            int64_t lddk, const void* dv, int64_t lddv, int has_amask, int Lq, int Lk, float drop_p, int dtype,
+                            int backward, char* out, int cap);
 
 /* ------------------------------------------------------------------ position encoding
  * pos[b][h*W+w][c] for the (B,H,W) uint8 mask (1 = padded): sine over the time axis H only,

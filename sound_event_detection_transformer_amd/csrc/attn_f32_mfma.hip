@@ -297,12 +297,26 @@ static bool af_on() {
   return v == 1;
 }
 
-// -1: outside the envelope (head dim 32 is implied by the callers; Lq, Lk <= 128; 16-byte aligned rows) - the caller uses the VALU kernel
+// The envelopes as host predicates (the launch paths below decide with them, and so does sedt_attention_describe, which runs those
+// paths in describe mode): head dim 32 is implied by the callers; Lq, Lk <= 128; every tensor the kernels touch as float4 has 16-byte
+// aligned rows
+static bool af_fwd_fits(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                        int Lq, int Lk) {
+  if (!af_on() || Lq > 128 || Lk > 128 || Lq < 1 || Lk < 1) return false;
+  return af_aligned(q, ldq) && af_aligned(k, ldk) && af_aligned(v, ldv) && af_aligned(o, ldo);
+}
+static bool af_bwd_fits(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
+                        const void* dout, int64_t lddo, const void* dq, int64_t lddq, const void* dk, int64_t lddk, const void* dv,
+                        int64_t lddv, int Lq, int Lk) {
+  if (!af_fwd_fits(q, ldq, k, ldk, v, ldv, o, ldo, Lq, Lk)) return false;
+  return af_aligned(dout, lddo) && af_aligned(dq, lddq) && af_aligned(dk, lddk) && af_aligned(dv, lddv);
+}
+
+// -1: outside the envelope - the caller uses the VALU kernel
 int attn_f32_fwd_try(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo, float* lse,
                      const uint8_t* kpm, const float* amask, int B, int H, int Lq, int Lk, float drop_p, uint32_t seed,
                      const uint32_t* seed_ptr, hipStream_t st) {
-  if (!af_on() || Lq > 128 || Lk > 128 || Lq < 1 || Lk < 1) return -1;
-  if (!af_aligned(q, ldq) || !af_aligned(k, ldk) || !af_aligned(v, ldv) || !af_aligned(o, ldo)) return -1;
+  if (!af_fwd_fits(q, ldq, k, ldk, v, ldv, o, ldo, Lq, Lk)) return -1;
   const int ntk = Lk <= 32 ? 1 : 4, LqP = (Lq + 31) & ~31;             // instances: one key tile (the decoder's self-attention) or four
   const size_t lds = ((size_t)(LqP + 2 * ntk * 32) * af::PT + ntk * 32) * sizeof(float);
   const float scale = 1.f / sqrtf((float)af::DH);
@@ -311,6 +325,7 @@ int attn_f32_fwd_try(const void* q, int64_t ldq, const void* k, int64_t ldk, con
   dim3 grid(B * H), block(256);
 #define SEDT_AFF1(NT_, AM_, DR_)                                                                                                          \
   {                                                                                                                                       \
+    SEDT_DESCRIBE("attn_f32_fwd_kernel<%d, %s, %s>", NT_, AM_ ? "true" : "false", DR_ ? "true" : "false");                                \
     static bool done = false;                                                                                                             \
     if (af_set_lds(attn_f32_fwd_kernel<NT_, AM_, DR_>, done, "attention_fwd (f32 mfma)")) return 1;                                       \
     hipLaunchKernelGGL((attn_f32_fwd_kernel<NT_, AM_, DR_>), grid, block, lds, st, (const float*)q, (long)ldq, (const float*)k, (long)ldk, \
@@ -331,10 +346,7 @@ int attn_f32_bwd_try(const void* q, int64_t ldq, const void* k, int64_t ldk, con
                      const void* dout, int64_t lddo, const float* lse, const uint8_t* kpm, const float* amask, void* dq, int64_t lddq,
                      void* dk, int64_t lddk, void* dv, int64_t lddv, int B, int H, int Lq, int Lk, float drop_p, uint32_t seed,
                      const uint32_t* seed_ptr, hipStream_t st) {
-  if (!af_on() || Lq > 128 || Lk > 128 || Lq < 1 || Lk < 1) return -1;
-  if (!af_aligned(q, ldq) || !af_aligned(k, ldk) || !af_aligned(v, ldv) || !af_aligned(o, ldo) || !af_aligned(dout, lddo) ||
-      !af_aligned(dq, lddq) || !af_aligned(dk, lddk) || !af_aligned(dv, lddv))
-    return -1;
+  if (!af_bwd_fits(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dq, lddq, dk, lddk, dv, lddv, Lq, Lk)) return -1;
   const int ntq = (Lq + 31) / 32, ntk = (Lk + 31) / 32;
   // instances: the query side 1 tile (the decoder's Q = 11 / 21 queries) or 4 (encoder), the key side 1 or 4
   const int NQ = ntq <= 1 ? 1 : 4, NK = ntk <= 1 ? 1 : 4;
@@ -345,6 +357,7 @@ int attn_f32_bwd_try(const void* q, int64_t ldq, const void* k, int64_t ldk, con
   dim3 grid(B * H, 2), block(256);
 #define SEDT_AFB1(NQ_, NK_, AM_, DR_)                                                                                                    \
   {                                                                                                                                      \
+    SEDT_DESCRIBE("attn_f32_bwd_kernel<%d, %d, %s, %s>", NQ_, NK_, AM_ ? "true" : "false", DR_ ? "true" : "false");                      \
     static bool done = false;                                                                                                            \
     if (af_set_lds(attn_f32_bwd_kernel<NQ_, NK_, AM_, DR_>, done, "attention_bwd (f32 mfma)")) return 1;                                 \
     hipLaunchKernelGGL((attn_f32_bwd_kernel<NQ_, NK_, AM_, DR_>), grid, block, lds, st, (const float*)q, (long)ldq, (const float*)k,      \

@@ -303,13 +303,31 @@ static int set_attr_once(K kern, bool& done, size_t bytes, const char* what) {
 
 static bool aligned_ok(const void* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 7) == 0; }
 
+// The envelopes of the MFMA kernels, as host predicates: the launch paths below and sedt_attention_describe (which runs the same
+// launch paths in describe mode) decide with them.  Forward: both lengths within 8 tiles of 32, q / k / v rows readable as 16-byte
+// chunks (o and lse are written element by element).  Returns the key tile count, 0 when outside.
+static int attn_fwd_mfma_tiles(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int Lq, int Lk) {
+  if (Lk < 1 || Lq < 1 || Lk > 32 * AMAXT || Lq > 32 * AMAXT) return 0;
+  if (!aligned_ok(q, ldq) || !aligned_ok(k, ldk) || !aligned_ok(v, ldv)) return 0;
+  return (Lk + 31) / 32;
+}
+// Backward: a 4 x 4 matrix of tile counts; q / k / v / dO staged and o read (the delta pre-pass) as 16-byte chunks, dk / dv written
+// as 8-byte groups (dq element by element)
+static bool attn_bwd_mfma_fits(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
+                               int64_t ldo, const void* dout, int64_t lddo, const void* dk, int64_t lddk, const void* dv, int64_t lddv,
+                               int Lq, int Lk) {
+  if (Lk < 1 || Lq < 1 || Lk > 128 || Lq > 128) return false;              // template matrix kept small: 4 x 4 tile counts
+  if (!aligned_ok(q, ldq) || !aligned_ok(k, ldk) || !aligned_ok(v, ldv) || !aligned_ok(dout, lddo) || !aligned_ok(o, ldo)) return false;
+  if ((lddk & 3) || (lddv & 3) || (reinterpret_cast<uintptr_t>(dk) & 7) || (reinterpret_cast<uintptr_t>(dv) & 7)) return false;
+  return true;
+}
+
 // returns -1 if outside the envelope (caller falls back to the generic kernels)
 int attn_fwd_mfma_try(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
                       float* lse, const uint8_t* kpm, const float* amask, int B, int H, int Lq, int Lk, float drop_p,
                       uint32_t seed, const uint32_t* seed_ptr, hipStream_t st) {
-  if (Lk > 32 * AMAXT || Lq > 32 * AMAXT) return -1;
-  if (!aligned_ok(q, ldq) || !aligned_ok(k, ldk) || !aligned_ok(v, ldv)) return -1;
-  const int nt = (Lk + 31) / 32, LqP = (Lq + 31) & ~31;
+  const int nt = attn_fwd_mfma_tiles(q, ldq, k, ldk, v, ldv, Lq, Lk), LqP = (Lq + 31) & ~31;
+  if (nt == 0) return -1;
   const int nwave = 4;     // all four waves stage K/V/Q; waves beyond the query tiles then idle
   const size_t lds = (size_t)(2 * nt * 32 + LqP) * AROW + (size_t)(nt * 32 + nwave * 32) * sizeof(float);
   const float scale = 1.f / sqrtf((float)AD);
@@ -318,6 +336,7 @@ int attn_fwd_mfma_try(const void* q, int64_t ldq, const void* k, int64_t ldk, co
   dim3 grid(B * H), block(64 * nwave);
 #define SEDT_AF1(NT_, AM_)                                                                                                 \
   {                                                                                                                        \
+    SEDT_DESCRIBE("attn_fwd_mfma_kernel<%d, %s>", NT_, AM_ ? "true" : "false");                                            \
     static bool done = false;                                                                                              \
     if (set_attr_once(attn_fwd_mfma_kernel<NT_, AM_>, done, 64 * 1024, "attention_fwd")) return 1;                         \
     hipLaunchKernelGGL((attn_fwd_mfma_kernel<NT_, AM_>), grid, block, lds, st, (const bf16_t*)q, (long)ldq, (const bf16_t*)k, \
@@ -345,6 +364,7 @@ static int launch_bwd_q(int ntk, dim3 grid, dim3 block, size_t lds, hipStream_t 
                         const uint32_t* seed_ptr) {
 #define SEDT_AB1(NTK_, AM_)                                                                                                \
   {                                                                                                                        \
+    SEDT_DESCRIBE("attn_bwd_mfma_kernel<%d, %d, %s>", NTQ, NTK_, AM_ ? "true" : "false");                                  \
     static bool done = false;                                                                                              \
     if (set_attr_once(attn_bwd_mfma_kernel<NTQ, NTK_, AM_>, done, 96 * 1024, "attention_bwd")) return 1;                   \
     hipLaunchKernelGGL((attn_bwd_mfma_kernel<NTQ, NTK_, AM_>), grid, block, lds, st, (const bf16_t*)q, (long)ldq,          \
@@ -369,9 +389,7 @@ int attn_bwd_mfma_try(const void* q, int64_t ldq, const void* k, int64_t ldk, co
                       int64_t ldo, const void* dout, int64_t lddo, const float* lse, const uint8_t* kpm, const float* amask,
                       void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int B, int H, int Lq, int Lk,
                       float drop_p, uint32_t seed, const uint32_t* seed_ptr, hipStream_t st) {
-  if (Lk > 128 || Lq > 128) return -1;                    // template matrix kept small: 4 x 4 tile counts
-  if (!aligned_ok(q, ldq) || !aligned_ok(k, ldk) || !aligned_ok(v, ldv) || !aligned_ok(dout, lddo)) return -1;
-  if ((lddk & 3) || (lddv & 3) || (reinterpret_cast<uintptr_t>(dk) & 7) || (reinterpret_cast<uintptr_t>(dv) & 7)) return -1;
+  if (!attn_bwd_mfma_fits(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dk, lddk, dv, lddv, Lq, Lk)) return -1;
   const int ntq = (Lq + 31) / 32, ntk = (Lk + 31) / 32;
   const size_t lds = (size_t)(2 * ntq * 32 + 2 * ntk * 32) * AROW + (size_t)(2 * ntq * 32 + ntk * 32) * sizeof(float);
   const int nwave = std::min(4, std::max(ntq, ntk));

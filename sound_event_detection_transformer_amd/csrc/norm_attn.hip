@@ -152,6 +152,14 @@ __global__ __launch_bounds__(1024) void ln_bwd_final_kernel(const float* __restr
   }
 }
 
+// every lane moves its D / 64 features of a row as ONE vector (VecT: 8 bytes for bf16 at D = 256, 16 for f32 at 256 and bf16 at 512, 32
+// for f32 at 512), so each tensor must start on that boundary (rows are contiguous: D elements apart); gamma / beta are f32 vectors of
+// the same element count.  A null pointer (an optional tensor) passes.
+static bool ln_aligned(const void* p, int D, int elem_bytes) {
+  return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(D / 64 * elem_bytes - 1)) == 0;
+}
+static int ln_elem_bytes(int dtype) { return dtype == SEDT_BF16 ? 2 : 4; }
+
 static int ln_bwd_blocks(int rows) {
   int b = (rows + 3) / 4;
   return b < 1 ? 1 : (b > 512 ? 512 : b);
@@ -415,12 +423,33 @@ static bool use_attn_mfma() {
 }
 }  // namespace sedt
 
+namespace sedt {
+// LDS the generic (VALU) kernels need: K and V (forward) or Q, K, V, dO (backward) as f32 rows plus the per-wave scratch strips.  Their
+// envelope is this figure against the 160 KiB of a workgroup; the launch paths and sedt_attention_describe both go through them.
+constexpr size_t ATTN_LDS_MAX = 160 * 1024;
+static size_t attn_fwd_generic_lds(int Lk) {
+  const int LkPad = (Lk + 63) & ~63;
+  return ((size_t)2 * Lk * KP + 4 * LkPad) * sizeof(float);
+}
+static size_t attn_bwd_generic_lds(int Lq, int Lk) {
+  const int LmPad = (std::max(Lq, Lk) + 63) & ~63;
+  return ((size_t)2 * Lq * KP + 2 * Lk * KP + 2 * Lq + 8 * LmPad) * sizeof(float);
+}
+}  // namespace sedt
+
 using namespace sedt;
 
 extern "C" int sedt_layernorm_fwd(const void* x, const float* gamma, const float* beta, const void* add, void* y, void* y2,
                                   float* mean, float* rstd, int rows, int D, int dtype, void* stream) {
   SEDT_REQUIRE(x && gamma && beta && y && mean && rstd, "layernorm_fwd: null pointer");
   SEDT_REQUIRE((y2 == nullptr) == (add == nullptr), "layernorm_fwd: y2 and add go together");
+  SEDT_REQUIRE((dtype == SEDT_F32 || dtype == SEDT_BF16) && (D == 256 || D == 512), "layernorm: unsupported dtype %d / width %d (256 or 512)",
+               dtype, D);
+  const int eb = ln_elem_bytes(dtype);
+  SEDT_REQUIRE(ln_aligned(x, D, eb) && ln_aligned(add, D, eb) && ln_aligned(y, D, eb) && ln_aligned(y2, D, eb) && ln_aligned(gamma, D, 4) &&
+                   ln_aligned(beta, D, 4),
+               "layernorm_fwd: x, add, y, y2 must be %d-byte aligned and gamma, beta %d-byte aligned (one vector access per lane)",
+               D / 64 * eb, D / 64 * 4);
   dim3 grid((rows + 3) / 4), block(256);
 #define A_(T) grid, block, 0, S(stream), (const T*)x, gamma, beta, (const T*)add, (T*)y, (T*)y2, mean, rstd, rows
   if (dtype == SEDT_F32 && D == 256) hipLaunchKernelGGL((ln_fwd_kernel<float, 4>), A_(float));
@@ -452,6 +481,13 @@ extern "C" int sedt_layernorm_bwd_drop(const void* dy, const void* dy2, const vo
                                        uint32_t seed, const uint32_t* seed_ptr, int dtype, void* stream) {
   SEDT_REQUIRE(dy && x && gamma && mean && rstd && dx, "layernorm_bwd: null pointer");
   SEDT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "layernorm_bwd: drop_p out of range");
+  SEDT_REQUIRE((dtype == SEDT_F32 || dtype == SEDT_BF16) && (D == 256 || D == 512), "layernorm: unsupported dtype %d / width %d (256 or 512)",
+               dtype, D);
+  const int eb = ln_elem_bytes(dtype);
+  SEDT_REQUIRE(ln_aligned(dy, D, eb) && ln_aligned(dy2, D, eb) && ln_aligned(x, D, eb) && ln_aligned(dres, D, eb) &&
+                   ln_aligned(dres2, D, eb) && ln_aligned(dx, D, eb) && ln_aligned(dx_drop, D, eb) && ln_aligned(gamma, D, 4),
+               "layernorm_bwd: dy, dy2, x, dres, dres2, dx, dx_drop must be %d-byte aligned and gamma %d-byte aligned (one vector access "
+               "per lane)", D / 64 * eb, D / 64 * 4);
   const uint32_t th = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
   const float ik = 1.f / (1.f - drop_p);
   SEDT_REQUIRE(scratch && scratch_bytes >= sedt_layernorm_bwd_scratch(rows, D), "layernorm_bwd: scratch too small");
@@ -490,9 +526,10 @@ extern "C" int sedt_attention_fwd(const void* q, int64_t ldq, const void* k, int
     int r = attn_f32_fwd_try(q, ldq, k, ldk, v, ldv, o, ldo, lse, kpm, amask, B, H, Lq, Lk, drop_p, seed, seed_ptr, S(stream));
     if (r >= 0) return r;
   }
-  const int LkPad = (Lk + 63) & ~63;
-  size_t lds = ((size_t)2 * Lk * KP + 4 * LkPad) * sizeof(float);
-  SEDT_REQUIRE(lds <= 160 * 1024, "attention_fwd: Lk=%d needs %zu B of LDS", Lk, lds);
+  const size_t lds = attn_fwd_generic_lds(Lk);
+  SEDT_REQUIRE(lds <= ATTN_LDS_MAX, "attention_fwd: Lk=%d needs %zu B of LDS", Lk, lds);
+  SEDT_REQUIRE(dtype == SEDT_F32 || dtype == SEDT_BF16, "attention_fwd: unsupported dtype %d", dtype);
+  SEDT_DESCRIBE("attn_fwd_kernel<%s>", dtype == SEDT_F32 ? "float" : "__bf16");
   const float scale = 1.f / sqrtf((float)DH);
   const uint32_t th = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
   const float ik = 1.f / (1.f - drop_p);
@@ -516,6 +553,7 @@ extern "C" int sedt_attention_bwd(const void* q, int64_t ldq, const void* k, int
                                   void* dv, int64_t lddv, int B, int H, int Lq, int Lk, float drop_p, uint32_t seed,
                                   const uint32_t* seed_ptr, int dtype, void* stream) {
   SEDT_REQUIRE(q && k && v && o && dout && lse && dq && dk && dv, "attention_bwd: null pointer");
+  SEDT_REQUIRE(Lk >= 1 && Lq >= 1, "attention_bwd: Lq=%d Lk=%d out of range", Lq, Lk);
   SEDT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention_bwd: drop_p out of range");
   if (dtype == SEDT_BF16 && use_attn_mfma()) {
     int r = attn_bwd_mfma_try(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, kpm, amask, dq, lddq, dk, lddk, dv, lddv, B, H, Lq,
@@ -527,9 +565,10 @@ extern "C" int sedt_attention_bwd(const void* q, int64_t ldq, const void* k, int
                              drop_p, seed, seed_ptr, S(stream));
     if (r >= 0) return r;
   }
-  const int LmPad = (std::max(Lq, Lk) + 63) & ~63;
-  size_t lds = ((size_t)2 * Lq * KP + 2 * Lk * KP + 2 * Lq + 8 * LmPad) * sizeof(float);
-  SEDT_REQUIRE(lds <= 160 * 1024, "attention_bwd: Lq=%d Lk=%d need %zu B of LDS", Lq, Lk, lds);
+  const size_t lds = attn_bwd_generic_lds(Lq, Lk);
+  SEDT_REQUIRE(lds <= ATTN_LDS_MAX, "attention_bwd: Lq=%d Lk=%d need %zu B of LDS", Lq, Lk, lds);
+  SEDT_REQUIRE(dtype == SEDT_F32 || dtype == SEDT_BF16, "attention_bwd: unsupported dtype %d", dtype);
+  SEDT_DESCRIBE("attn_bwd_kernel<%s>", dtype == SEDT_F32 ? "float" : "__bf16");
   const float scale = 1.f / sqrtf((float)DH);
   const uint32_t th = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
   const float ik = 1.f / (1.f - drop_p);
@@ -548,4 +587,32 @@ extern "C" int sedt_attention_bwd(const void* q, int64_t ldq, const void* k, int
                        ik, seed, seed_ptr);
   } else { set_error("attention_bwd: unsupported dtype %d", dtype); return 1; }
   return check_launch("attention_bwd");
+}
+
+// The kernel instance sedt_attention_fwd (backward = 0) or sedt_attention_bwd (backward = 1) launches for these pointers, strides, lengths,
+// dropout and dtype: the entry point itself runs in describe mode (csrc/common.h), so every envelope rule is the launch path's own.
+// Pointers are only compared and tested for alignment.
+extern "C" int sedt_attention_describe(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
+                                       int64_t ldo, const void* dout, int64_t lddo, const void* dq, int64_t lddq, const void* dk,
+                                       int64_t lddk, const void* dv, int64_t lddv, int has_amask, int Lq, int Lk, float drop_p, int dtype,
+                                       int backward, char* out, int cap) {
+  SEDT_REQUIRE(out && cap > 0, "attention_describe: bad arguments");
+  out[0] = 0;
+  alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};      // stands in for lse / amask: never read
+  float* lse = const_cast<float*>(dummy);
+  const float* amask = has_amask ? dummy : nullptr;
+  describe.on = true;
+  describe.name[0] = 0;
+  const int r = backward ? sedt_attention_bwd(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, nullptr, amask, const_cast<void*>(dq), lddq,
+                                              const_cast<void*>(dk), lddk, const_cast<void*>(dv), lddv, 1, 1, Lq, Lk, drop_p, 0u, nullptr,
+                                              dtype, nullptr)
+                         : sedt_attention_fwd(q, ldq, k, ldk, v, ldv, const_cast<void*>(o), ldo, lse, nullptr, amask, 1, 1, Lq, Lk, drop_p,
+                                              0u, nullptr, dtype, nullptr);
+  describe.on = false;
+  if (r == 0 && describe.name[0] == 0) {
+    set_error("attention_describe: no kernel instance reported");
+    return 1;
+  }
+  if (r == 0) snprintf(out, cap, "%s", describe.name);
+  return r;
 }

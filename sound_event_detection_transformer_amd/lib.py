@@ -154,6 +154,7 @@ SIGNATURES = {
                                 _vp, _i, _vp]),
     'sedt_attention_bwd': (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                 _i64, _vp, _i64, _i, _i, _i, _i, _f, _u32, _vp, _i, _vp]),
+    'sedt_attention_describe': (_i, [_vp, _i64] * 8 + [_i, _i, _i, _f, _i, _i, C.c_char_p, _i]),
     'sedt_pack_frag': (_i, [_vp, _i, _i, _vp]),
     'sedt_encoder_slab_ok': (_i, [_i, _i, _i, _i, _i]),
     'sedt_encoder_qkv_fwd': (_i, [_vp] * 12 + [_i, _i, C.POINTER(SedtPrefetch), _vp]),

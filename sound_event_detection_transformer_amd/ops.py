@@ -1105,6 +1105,7 @@ def sigmoid_grad(g, s):
 def layernorm_fwd(dtype, x, gamma, beta, add_t=None, out=None):
     """out = (y, mean, rstd) preallocated (contiguous row ranges of larger buffers are fine)"""
     rows, D = x.shape
+    assert x.is_contiguous() and (add_t is None or (add_t.is_contiguous() and add_t.shape == x.shape)), 'layernorm_fwd: contiguous rows'
     y2 = torch.empty_like(x) if add_t is not None else None
     if out is not None:
         y, mean, rstd = out
@@ -1112,6 +1113,7 @@ def layernorm_fwd(dtype, x, gamma, beta, add_t=None, out=None):
         y = torch.empty_like(x)
         mean = torch.empty((rows,), device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
+    assert y.is_contiguous() and y.shape == x.shape, 'layernorm_fwd: contiguous rows'
     L.check(L.load().sedt_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(add_t), _p(y), _p(y2), _p(mean), _p(rstd), rows, D,
                                         dtype, L.stream_ptr()), 'layernorm_fwd')
     return y, y2, mean, rstd
@@ -1124,6 +1126,7 @@ def layernorm_bwd(dtype, dy, x, gamma, mean, rstd, dy2=None, dres=None, want_par
     dropped output fed this LayerNorm) as a 4th result - one launch instead of layernorm_bwd + dropout_grad"""
     lib = L.load()
     rows, D = x.shape
+    assert all(t is None or (t.is_contiguous() and t.shape == x.shape) for t in (dy, x, dy2, dres, dres2)), 'layernorm_bwd: contiguous rows'
     dx = torch.empty_like(x)
     dg = torch.empty((D,), device=x.device, dtype=torch.float32) if want_param_grads else None
     db = torch.empty((D,), device=x.device, dtype=torch.float32) if want_param_grads else None
@@ -1150,11 +1153,24 @@ def layernorm_bwd(dtype, dy, x, gamma, mean, rstd, dy2=None, dres=None, want_par
     return dx, dg, db
 
 
+def attention_instance(dtype, q, k, v, o, Lq, Lk, amask=None, drop_p=0.0, do=None, dq=None, dk=None, dv=None):
+    """the kernel instance attention_fwd (do is None) or attention_bwd launches for these tensors ('' if the call would be refused):
+    sedt_attention_describe, nothing is launched"""
+    def pl(t):
+        return (_p(t), t.stride(0)) if t is not None else (None, 0)
+    buf = C.create_string_buffer(96)
+    args = pl(q) + pl(k) + pl(v) + pl(o) + pl(do) + pl(dq) + pl(dk) + pl(dv)
+    L.load().sedt_attention_describe(*args, int(amask is not None), Lq, Lk, drop_p, dtype, int(do is not None), buf, 96)
+    return buf.value.decode()
+
+
 def attention_fwd(dtype, q, k, v, B, H, Lq, Lk, kpm=None, amask=None, drop_p=0.0, seed=0, seed_ptr=None, out=None):
     """q [B*Lq, >=H*32] / k, v [B*Lk, ...] row-strided views; returns (o [B*Lq, H*32], lse [B,H,Lq])"""
     if out is None:
         out = torch.empty((B * Lq, H * 32), device=q.device, dtype=q.dtype)
     lse = torch.empty((B, H, Lq), device=q.device, dtype=torch.float32)
+    if L.LAUNCH_LOG is not None:     # (lib.launch_log(): which kernel instance the dispatcher picks for this problem)
+        L.LAUNCH_LOG['attention:' + attention_instance(dtype, q, k, v, out, Lq, Lk, amask, drop_p)] += 1
     L.check(L.load().sedt_attention_fwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(out), out.stride(0),
                                         _p(lse), _p(kpm), _p(amask), B, H, Lq, Lk, drop_p, seed & 0xffffffff, _p(seed_ptr),
                                         dtype, L.stream_ptr()), 'attention_fwd')
@@ -1163,6 +1179,8 @@ def attention_fwd(dtype, q, k, v, B, H, Lq, Lk, kpm=None, amask=None, drop_p=0.0
 
 def attention_bwd(dtype, q, k, v, o, do, lse, B, H, Lq, Lk, dq, dk, dv, kpm=None, amask=None, drop_p=0.0, seed=0,
                   seed_ptr=None):
+    if L.LAUNCH_LOG is not None:
+        L.LAUNCH_LOG['attention:' + attention_instance(dtype, q, k, v, o, Lq, Lk, amask, drop_p, do, dq, dk, dv)] += 1
     L.check(L.load().sedt_attention_bwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
                                         _p(do), do.stride(0), _p(lse), _p(kpm), _p(amask), _p(dq), dq.stride(0), _p(dk),
                                         dk.stride(0), _p(dv), dv.stride(0), B, H, Lq, Lk, drop_p, seed & 0xffffffff,
