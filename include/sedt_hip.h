@@ -52,6 +52,8 @@ extern "C" {
  * exact-f32 mode.  The "bf16x3" compute mode (runtime.set_compute_dtype('bf16x3')): f32 activations and gradients everywhere,
  * this code for the contractions; meets the 1e-3 parity tolerance (tests/test_x3_gpu.py). */
 #define SEDT_BF16X3 2
+/* sedt_mel_spectrogram only: the waveform as 16-bit PCM, a sample worth x / 32768 */
+#define SEDT_I16 3
 
 #define SEDT_ACT_NONE 0
 #define SEDT_ACT_RELU 1
@@ -870,6 +872,27 @@ int sedt_box_transform_views(const float* amp, int64_t raw_stride, const void* a
  * frames * F * 4 + 2 * G * F * 8 + 64 bytes <= 160 KB of LDS, F <= 1024; otherwise an error. */
 int sedt_scaler_update(const float* amp, int64_t raw_stride, const int32_t* nframes_raw, int B, int frames, int F, int apply_log,
                        double* clip_stats, double* acc, int64_t* count, void* stream);
+/* sedt_mel_spectrogram: waveform -> mel amplitudes, what the reference's load_and_compute_mel_spec (data_utils/SedData.py:195-217,
+ * compute_log=False) gets from librosa - stft(n_fft, hop, win_length = n_window, window = hamming, center = True, pad_mode =
+ * 'reflect'), magnitude, filters.mel(htk = False, norm = None), transposed - for a whole batch in ONE launch:
+ *   frame t of clip b (t < nframes[b] = 1 + nsamples[b] / hop) = padded samples [t hop, t hop + n_fft), padded index q being sample
+ *   q - n_fft/2 reflected at the clip's ends (j < 0 -> -j; j >= n -> 2 (n - 1) - j); times window[i] (f32 [n_fft]: the n_window-point
+ *   window centred, zeros left of (n_fft - n_window) / 2 and right of it - the kernel reads only the samples under it);
+ *   S = |rfft|, n_fft/2 + 1 bins, by an n_fft/2-point complex f32 FFT in LDS (radix-4 Stockham) and the real-input split;
+ *   out[b][t][m] = sum_i band_w[band_off[m] + i] * S[band_bin0[m] + i], i = 0 .. band_off[m + 1] - band_off[m] - 1 in that order.
+ * wave [B][wave_stride] f32 (SEDT_F32) or int16 PCM (SEDT_I16: sample = x / 32768, so an int16 batch gives the bits of the f32 batch
+ * x / 32768); nsamples int32 [B] DEVICE memory (clamped to 1 .. wave_stride; the caller, who knows the lengths, refuses a clip shorter
+ * than n_fft/2 + 1 samples, which would need a second reflection).  out f32 [B][out_rows][n_mels]: rows nframes[b] .. out_rows - 1
+ * are written as 0, frames past out_rows are dropped.  Tables, all device memory, made once on the host in float64 and rounded
+ * (utilities/mel.py mel_tables): window f32 [n_fft]; twiddle f32 [2][n_fft/2 + 1] = cos and -sin of 2 pi t / n_fft - no device
+ * sincos; band_bin0 int32 [n_mels], band_off int32 [n_mels + 1], band_w f32 [n_weights] - the filterbank's non-zero run of every band.
+ * A workgroup owns 4 consecutive frames of one clip; no floating-point atomics, so a clip's bits depend neither on B nor on the other
+ * clips.  No allocation, no synchronisation, capturable.  Envelope (sedt_mel_ok, 1 = inside): n_fft 512, 1024 or 2048;
+ * 1 <= n_window <= n_fft; hop >= 1; 1 <= n_mels <= 128.  B <= 65535. */
+int sedt_mel_ok(int n_fft, int n_window, int hop, int n_mels);
+int sedt_mel_spectrogram(const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* nsamples, int B, float* out,
+                         int out_rows, const float* window, const float* twiddle, const int32_t* band_bin0, const int32_t* band_off,
+                         const float* band_w, int n_weights, int n_fft, int n_window, int hop, int n_mels, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

@@ -13,6 +13,7 @@ if os.environ.get('SEDT_LIB_AB') and os.environ.get('SEDT_DEV') == '1':   # deve
 
 F32, BF16 = 0, 1
 BF16X3 = 2            # GEMM entry points only: f32 tensors, split-bf16 products (include/sedt_hip.h)
+I16 = 3               # sedt_mel_spectrogram only: the waveform as 16-bit PCM
 GEMM_X3 = False       # runtime.set_compute_dtype('bf16x3'): the f32 mode's contractions go through the BF16X3 code
 
 
@@ -210,6 +211,8 @@ SIGNATURES = {
     'sedt_box_transform': (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     'sedt_box_transform_views': (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _u32, _vp, C.c_uint64, _vp, _vp, _vp]),
     'sedt_scaler_update': (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'sedt_mel_ok': (_i, [_i, _i, _i, _i]),
+    'sedt_mel_spectrogram': (_i, [_vp, _i, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_query_patches': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),

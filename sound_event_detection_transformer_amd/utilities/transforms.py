@@ -35,6 +35,16 @@ def stage_clips(clips, n_mels, dev, staging=None):
     return host.to(dev, non_blocking=True), B, stride, nraw
 
 
+def _rows(nraw, nframes, stride):
+    """the rows per clip of a staged batch: ``nframes`` where the caller gives them, else what stage_clips found"""
+    if nframes is None:
+        return nraw
+    nframes = [int(n) for n in nframes]
+    if len(nframes) != len(nraw) or min(nframes, default=0) < 0 or max(nframes, default=0) > stride:
+        raise ValueError('nframes: one row count per clip, within the rows of the batch')
+    return nframes
+
+
 class PinnedRing(object):
     """small per-batch records (bytes) through a ring of PINNED staging buffers: a copy from pageable memory blocks the host until
     everything queued before it has run - the host would lose its run-ahead over the GPU on every batch (measured on the C5
@@ -152,10 +162,12 @@ class DeviceBoxTransform(object):
             rows.append((n, tm_t, tm_t0, fm_f, fm_f0, fm_on, fs, 0))
         return np.asarray(rows, np.int32).view(_AUG).reshape(-1)
 
-    def __call__(self, clips, params=None, out=None, staging=None):
+    def __call__(self, clips, params=None, out=None, staging=None, nframes=None):
         """clips: list of (T_raw, n_mels) float arrays / tensors (mel amplitudes), or a (B, T_raw, n_mels) tensor already on
-        the device.  params: optional structured array of _AUG records (else drawn).  Returns (B, 1, frames, n_mels) f32."""
+        the device.  params: optional structured array of _AUG records (else drawn).  nframes: the rows each clip of a device
+        tensor really has (else T_raw) - what DeviceMelSpectrogram returns beside its batch.  Returns (B, 1, frames, n_mels) f32."""
         amp, B, stride, nraw = stage_clips(clips, self.F, self.dev, staging)
+        nraw = _rows(nraw, nframes, stride)
         if params is None:
             params = self.draw_batch(nraw)
         params = np.ascontiguousarray(params)
@@ -247,12 +259,13 @@ class DeviceViewTransform(DeviceBoxTransform):
             rows.append((n, 0, 0) + fm[0] + (fs[0], 0) + (n, tm_t, tm_t0) + fm[1] + (fs[1], 0) + (noise_on, 0))
         return np.asarray(rows, np.int32).reshape(-1, 18).view(_VAUG).reshape(-1), normals
 
-    def __call__(self, clips, params=None, out=None, staging=None, normals=None):
-        """clips, staging: as DeviceBoxTransform.  params: optional _VAUG records (else drawn).  normals: the injected standard
+    def __call__(self, clips, params=None, out=None, staging=None, normals=None, nframes=None):
+        """clips, staging, nframes: as DeviceBoxTransform.  params: optional _VAUG records (else drawn).  normals: the injected standard
         normals, a list of per-clip (T_raw, F) arrays (None entries allowed) or a (B, stride, F) f32 device tensor; None with params
         given, or in mode 'device', makes the kernel draw them.  out: optional pair of (B, 1, frames, F) f32 tensors.
         Returns (x_teacher, x_student)."""
         amp, B, stride, nraw = stage_clips(clips, self.F, self.dev, staging)
+        nraw = _rows(nraw, nframes, stride)
         if params is None:
             params, normals = self.draw_batch(nraw)
         params = np.ascontiguousarray(params)
