@@ -25,10 +25,17 @@ inline const char* dev_getenv(const char* name) {
   return nullptr;
 #endif
 }
+// the integer value of a switch, `dflt` when it is not set (always, in the product).  A site reads it once:
+//   static const int mink = dev_int("SEDT_IGEMM_BN128_MINK", 512);
+inline int dev_int(const char* name, int dflt) {
+  const char* e = dev_getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
-// ---- describe mode (sedt_igemm_describe): while `describe.on`, every GEMM launcher writes the name of the kernel instance it WOULD
-// launch for the problem (as a profiler prints it) and returns 0 without launching - bench.py uses it to attach algorithmic flops and
-// bytes to the per-kernel times of the measured step (roofline.families).
+// ---- describe mode (sedt_igemm_describe, sedt_attention_describe): while `describe.on`, the launchers of the register-staged general
+// GEMM and of the attention kernels write the name of the kernel instance they WOULD launch for the problem (as a profiler prints it)
+// and return 0 without launching - bench.py uses it to attach algorithmic flops and bytes to the per-kernel times of the measured step
+// (roofline.families).  The LDS-DMA GEMM family has no such mode: its label is its plan (lds_gemm_common.h: LdsPlan).
 struct Describe {
   bool on;
   char name[96];

@@ -621,8 +621,8 @@ static int launch_typed(const SedtIgemm& p, hipStream_t st) {
     // (larger tiles - 24 instead of 6 MFMAs per wave between two barriers - measured SLOWER, before and after the loader clean-up of
     // round 4 (tools/dev/ab_gen_tile.sh, C2 step: 64x64 everywhere 26.1 ms bf16x3 / 28.1 ms f32; 128x64 above 512 tiles 29.9 / 30.2;
     // 128x128 above 512 tiles 31.8 / 30.0; above 256 tiles 34.3-34.5 / 31.2-31.9): what the pipeline needs is resident workgroups)
-    static int gen_tile = [] { const char* e = dev_getenv("SEDT_GEN_TILE"); return e ? atoi(e) : 0; }();      // developer A/B: 128064 / 128128
-    static int gen_min = [] { const char* e = dev_getenv("SEDT_GEN_TILE_MIN"); return e ? atoi(e) : 512; }();
+    static const int gen_tile = dev_int("SEDT_GEN_TILE", 0);      // developer A/B: 128064 / 128128
+    static const int gen_min = dev_int("SEDT_GEN_TILE_MIN", 512);
     if (gen_tile && sizeof(T) == 4) {
       const int tm = gen_tile / 1000 >= 128 ? 128 : 64, tn = gen_tile % 1000 >= 128 ? 128 : 64;
       if (p.M % tm == 0 && p.N % tn == 0 && (long)(p.M / tm) * (p.N / tn) * (p.splitk > 1 ? p.splitk : 1) >= gen_min) { bm = tm; bn = tn; }
@@ -644,7 +644,18 @@ static int launch_typed(const SedtIgemm& p, hipStream_t st) {
 
 }  // namespace sedt
 
-namespace sedt { int igemm_lds_try(const SedtIgemm& p, hipStream_t st); }   // igemm3.hip: the LDS-DMA GEMM family's dispatcher
+#include "wgrad3_body.h"           // LdsPlan / lds_plan / lds_launch (lds_gemm_common.h), WgradGroup
+namespace sedt {
+thread_local Describe describe = {false, {0}};
+// igemm3.hip / wgrad3.hip / wgrad4.hip: the grouped forms of the LDS-DMA family
+int igemm3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st);
+void igemm3_group_describe(const SedtIgemm* jobs, int njobs, char* out, size_t cap);
+int wgrad3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st);
+int wgrad3_group_build(const SedtIgemm* jobs, int njobs, WgradGroup* g);
+int wgrad_group_class(const SedtIgemm& p, unsigned* a_bytes, unsigned* b_bytes);
+bool wgrad4_shape_ok(int M, int N);
+int wgrad4_tile_m(int M, int N);
+}
 
 // SedtIgemm.rmap (the residual on a coarser grid) is honoured by every kernel behind sedt_igemm / sedt_igemm_group / sedt_igemm_co that reads
 // `res`; what they rely on is checked here, once, for all of them
@@ -667,50 +678,44 @@ static int check_rmap(const SedtIgemm& p) {
   return 0;
 }
 
-static bool use_lds_family() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM_LDS");       // developer A/B switch: 0 = the general kernel of this file for everything
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-extern "C" int sedt_igemm(const SedtIgemm* args, int dtype, void* stream) {
+// The argument checks of sedt_igemm, then the plan: *lds = the LDS-DMA family (igemm3 / wgrad3 / wgrad4) takes the problem, on *plan;
+// otherwise the general kernel of this file does (igemm_general)
+static int igemm_plan(const SedtIgemm* args, int dtype, sedt::LdsContext ctx, bool* lds, sedt::LdsPlan* plan) {
   using namespace sedt;
   SEDT_REQUIRE(args != nullptr, "igemm: null args");
   SEDT_REQUIRE(args->M > 0 && args->N > 0 && args->K > 0, "igemm: bad dims M=%d N=%d K=%d", args->M, args->N, args->K);
   SEDT_REQUIRE(args->A && args->B && (args->C || args->splitk > 1), "igemm: null operand");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int r = check_rmap(*args)) return r;
   if (dtype != SEDT_BF16)
     SEDT_REQUIRE(!args->omap && !args->btap_on && !args->f32ep && !args->awrap, "igemm: omap / btap / f32ep / awrap are features of the bf16 LDS-DMA kernels");
-  if (dtype == SEDT_F32) {
-    SEDT_REQUIRE(args->colsum_out == nullptr, "igemm: colsum_out is a bf16-only feature");
-    return launch_typed<float>(*args, st);
-  }
-  if (dtype == SEDT_BF16X3) {           // f32 tensors, split-bf16 products (see the header of this file)
-    SEDT_REQUIRE(args->colsum_out == nullptr, "igemm: colsum_out is a bf16-only feature");
-    return launch_typed<float, true>(*args, st);
+  static const int lds_family = dev_int("SEDT_IGEMM_LDS", 1);       // developer A/B switch: 0 = the general kernel of this file for everything
+  *lds = dtype == SEDT_BF16 && lds_family && lds_plan(*args, ctx, plan);
+  return 0;
+}
+
+// the register-staged kernel; in describe mode (a null stream then) its launcher only writes the instance's name
+static int igemm_general(const SedtIgemm& a, int dtype, hipStream_t st) {
+  using namespace sedt;
+  if (dtype == SEDT_F32 || dtype == SEDT_BF16X3) {           // BF16X3: f32 tensors, split-bf16 products (see the header of this file)
+    SEDT_REQUIRE(a.colsum_out == nullptr, "igemm: colsum_out is a bf16-only feature");
+    return dtype == SEDT_F32 ? launch_typed<float>(a, st) : launch_typed<float, true>(a, st);
   }
   if (dtype == SEDT_BF16) {
-    if (use_lds_family()) {               // LDS-DMA kernels (igemm3 / wgrad3 / wgrad4) when the problem fits their envelope
-      int r = igemm_lds_try(*args, st);
-      if (r >= 0) return r;
-    }
-    SEDT_REQUIRE(args->colsum_out == nullptr, "igemm: colsum_out needs the bf16 LDS-DMA wgrad kernel (M,N,lda,ldb %% 8 == 0)");
-    SEDT_REQUIRE(!args->omap && !args->btap_on && !args->f32ep && !args->awrap,
-                 "igemm: omap / btap / f32ep / awrap problem outside the LDS-DMA envelope (M %d N %d K %d)", args->M, args->N, args->K);
-    return launch_typed<bf16_t>(*args, st);
+    SEDT_REQUIRE(a.colsum_out == nullptr, "igemm: colsum_out needs the bf16 LDS-DMA wgrad kernel (M,N,lda,ldb %% 8 == 0)");
+    SEDT_REQUIRE(!a.omap && !a.btap_on && !a.f32ep && !a.awrap,
+                 "igemm: omap / btap / f32ep / awrap problem outside the LDS-DMA envelope (M %d N %d K %d)", a.M, a.N, a.K);
+    return launch_typed<bf16_t>(a, st);
   }
   set_error("igemm: unsupported dtype %d", dtype);
   return 1;
 }
 
-namespace sedt {
-thread_local Describe describe = {false, {0}};
-bool wgrad4_ok(const SedtIgemm& p);
-int wgrad_lds_envelope(const SedtIgemm& p, long* a_bytes, long* b_bytes);
+extern "C" int sedt_igemm(const SedtIgemm* args, int dtype, void* stream) {
+  bool lds;
+  sedt::LdsPlan plan;
+  if (int r = igemm_plan(args, dtype, sedt::LDS_SINGLE, &lds, &plan)) return r;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return lds ? sedt::lds_launch(plan, *args, st) : igemm_general(*args, dtype, st);
 }
 
 // name of the kernel instance sedt_igemm (grouped == 0), sedt_igemm_group (1: forward / dgrad) or sedt_wgrad_group (1: trans) runs
@@ -719,26 +724,25 @@ extern "C" int sedt_igemm_describe(const SedtIgemm* args, int dtype, int grouped
   using namespace sedt;
   SEDT_REQUIRE(args && out && cap > 0, "igemm_describe: bad arguments");
   out[0] = 0;
-  if (grouped && dtype == SEDT_BF16 && args->trans) {       // sedt_wgrad_group: the 256/128x128 group or the 64x64 group
-    long a, b;
-    if (wgrad_lds_envelope(*args, &a, &b) == 0) {
-      snprintf(out, cap, "%s", wgrad4_ok(*args) ? "wgrad4_group_kernel" : "wgrad3_group_kernel");
+  unsigned a, b;
+  if (grouped && dtype == SEDT_BF16 && args->trans)         // sedt_wgrad_group: the 256/128x128 group or the 64x64 group
+    if (const int cls = wgrad_group_class(*args, &a, &b)) {
+      snprintf(out, cap, "%s", cls == 4 ? "wgrad4_group_kernel" : "wgrad3_group_kernel");
       return 0;
     }
+  bool lds;
+  LdsPlan plan;
+  if (int r = igemm_plan(args, dtype, LDS_SINGLE, &lds, &plan)) return r;
+  if (lds) {
+    lds_plan_name(plan, out, cap);
+    return 0;
   }
   describe.on = true;
   describe.name[0] = 0;
-  const int r = sedt_igemm(args, dtype, nullptr);
+  const int r = igemm_general(*args, dtype, nullptr);
   describe.on = false;
   if (r == 0) snprintf(out, cap, "%s", describe.name);
   return r;
-}
-
-namespace sedt {
-int wgrad3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st);
-bool wgrad4_shape_ok(int M, int N);
-int wgrad4_tile_m(int M, int N);
-int igemm3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st);
 }
 
 extern "C" int sedt_igemm_group(const SedtIgemm* jobs, int njobs, int dtype, void* stream) {
@@ -756,16 +760,10 @@ extern "C" int sedt_igemm_group(const SedtIgemm* jobs, int njobs, int dtype, voi
 
 // the kernel instance sedt_igemm_group would run the problems on ("" when they fall back to one launch each); nothing is launched
 extern "C" int sedt_igemm_group_describe(const SedtIgemm* jobs, int njobs, int dtype, char* out, int cap) {
-  using namespace sedt;
   SEDT_REQUIRE(jobs && njobs >= 1 && out && cap > 0, "igemm_group_describe: bad arguments");
   out[0] = 0;
-  if (dtype != SEDT_BF16 || njobs < 2) return 0;
-  describe.on = true;
-  describe.name[0] = 0;
-  const int r = igemm3_group_try(jobs, njobs, nullptr);
-  describe.on = false;
-  if (r == 0) snprintf(out, cap, "%s", describe.name);
-  return r > 0 ? r : 0;
+  if (dtype == SEDT_BF16 && njobs >= 2) sedt::igemm3_group_describe(jobs, njobs, out, cap);
+  return 0;
 }
 
 extern "C" int sedt_wgrad_group(const SedtIgemm* jobs, int njobs, int dtype, void* stream) {
@@ -782,31 +780,22 @@ extern "C" int sedt_wgrad_group(const SedtIgemm* jobs, int njobs, int dtype, voi
 
 // forward / dgrad GEMM `main` with up to 10 weight-gradient problems riding in the same launch (igemm3_co_kernel).  Falls
 // back to separate launches whenever either side is outside its fast kernel's envelope - the results are the same.
-#include "wgrad3_body.h"
-namespace sedt {
-int wgrad3_group_build(const SedtIgemm* jobs, int njobs, WgradGroup* g);
-extern thread_local const WgradGroup* co_group;
-extern thread_local bool co_taken;
-}
-
+// With a rider group built, the main GEMM plans as LDS_CARRIER - that is, onto the 4-wave program - even where the instance it then
+// gets cannot carry the riders (*taken = 0: the caller keeps them)
 extern "C" int sedt_igemm_co(const SedtIgemm* main, const SedtIgemm* wjobs, int nw, int dtype, void* stream, int* taken) {
   using namespace sedt;
   SEDT_REQUIRE(main && (nw == 0 || wjobs) && taken, "igemm_co: bad arguments");
   *taken = 0;
   for (int i = 0; i < nw; ++i) SEDT_REQUIRE(!wjobs[i].rmap, "igemm_co: a weight-gradient rider takes no residual map (job %d)", i);
-  if (nw == 0) return sedt_igemm(main, dtype, stream);
-  static int on = -1;
-  if (on < 0) {
-    const char* e = sedt::dev_getenv("SEDT_COSCHEDULE");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
+  static const int on = dev_int("SEDT_COSCHEDULE", 1);
   WgradGroup g;
-  bool grouped = on && dtype == SEDT_BF16 && main->trans == 0 && wgrad3_group_build(wjobs, nw, &g) == 0;
-  co_taken = false;
-  co_group = grouped ? &g : nullptr;
-  const int r = sedt_igemm(main, dtype, stream);
-  co_group = nullptr;
-  *taken = co_taken ? 1 : 0;          // 0: the main GEMM ran on a kernel that cannot carry riders; the caller keeps them
+  if (nw == 0 || !on || dtype != SEDT_BF16 || main->trans != 0 || wgrad3_group_build(wjobs, nw, &g) != 0) return sedt_igemm(main, dtype, stream);
+  bool lds, took = false;
+  LdsPlan plan;
+  if (int r = igemm_plan(main, dtype, LDS_CARRIER, &lds, &plan)) return r;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int r = lds ? lds_launch(plan, *main, st, &g, &took) : igemm_general(*main, dtype, st);
+  *taken = took ? 1 : 0;
   return r;
 }
 
@@ -814,11 +803,7 @@ extern "C" int sedt_igemm_splitk(int M, int N, int K, int dtype) {
   // wgrad outputs are small (Cout x taps*Cin) while K (pixels) is long: split K until ~TARGET workgroups of 64x64,
   // keeping at least 4 K tiles per slice.  Every split costs a 64x64 f32 partial tile written and re-read, so the target
   // balances occupancy against slab traffic (measured on the full step: SEDT_SPLITK_TARGET sweep)
-  static int target_env = -2;
-  if (target_env == -2) {
-    const char* e = sedt::dev_getenv("SEDT_SPLITK_TARGET");
-    target_env = e ? atoi(e) : -1;
-  }
+  static const int target_env = sedt::dev_int("SEDT_SPLITK_TARGET", -1);
   // bf16: wgrads of a layer are issued as one grouped launch, so the union of their tiles fills the chip and each problem
   // needs less splitting (re-tuned: 192 -> 9407, 384 -> 9489, 512 -> 9457, 768 -> 9356, 1024 -> 9250 clips/s);
   // f32 parity mode launches them one by one on the register-staged kernel and keeps the larger target
@@ -829,11 +814,7 @@ extern "C" int sedt_igemm_splitk(int M, int N, int K, int dtype) {
   // the large problems run on 256x128 / 128x128 tiles (wgrad4.hip), one 8-wave workgroup per CU
   int tgt = target;
   if (dtype == SEDT_BF16 && sedt::wgrad4_shape_ok(M, N)) {
-    static int wide_env = -2;
-    if (wide_env == -2) {
-      const char* e = sedt::dev_getenv("SEDT_SPLITK_TARGET_WIDE");
-      wide_env = e ? atoi(e) : -1;
-    }
+    static const int wide_env = sedt::dev_int("SEDT_SPLITK_TARGET_WIDE", -1);
     tiles = (long)(M / sedt::wgrad4_tile_m(M, N)) * (N / 128);
     tgt = wide_env > 0 ? wide_env : (sedt::wgrad4_tile_m(M, N) == 256 ? 64 : 128);
   }
@@ -850,11 +831,7 @@ extern "C" int sedt_igemm_splitk(int M, int N, int K, int dtype) {
   // full (PMC: the wgrad launches fetched 8x their algorithmic bytes).  The price is more f32 slabs; take it when the
   // estimated fabric traffic drops by a fifth: operands A = K*M*2 B (dY), B = K*Cin*2 B (X; 3x3 kernels re-use a pixel for
   // 9 taps), slabs 2 * s * M*N*4 B (written, then read by the reduction).
-  static int kslice = -1;
-  if (kslice < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD_KSLICE");
-    kslice = (e && e[0] == '1') ? 1 : 0;      // opt-in: measured -33 % fetched bytes for the wgrad launches, same run time
-  }
+  static const int kslice = sedt::dev_int("SEDT_WGRAD_KSLICE", 0);      // opt-in: measured -33 % fetched bytes for the wgrad launches, same run time
   if (kslice && dtype == SEDT_BF16) {
     const int taps = (N % 9 == 0 && (N / 9) % 64 == 0) ? 9 : 1;
     const double A = 2.0 * K * M, B = 2.0 * K * (N / taps);

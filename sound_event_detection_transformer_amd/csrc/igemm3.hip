@@ -741,71 +741,6 @@ __global__ __launch_bounds__(1024) void igemm3_w16_kernel(const SedtIgemm p, con
   igemm3_body<BM, BN, S, 8, 1, 2>(p, a_bytes, b_bytes, blockIdx.x);
 }
 
-template <int BM, int BN, int S>
-static int launch3_w16(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
-  SEDT_DESCRIBE("igemm3_w16_kernel<%d, %d, %d>", BM, BN, S);
-  constexpr size_t ring = (size_t)2 * S * (BM + BN) * ROWB;
-  constexpr size_t ctile = (size_t)4 * BM * (BN + 4) * sizeof(float);
-  constexpr size_t lds = ring > ctile ? ring : ctile;
-  static bool attr_set = false;
-  auto kern = igemm3_w16_kernel<BM, BN, S>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("igemm3 w16: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  const int nwg = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(1024), lds, st, p, a_bytes, b_bytes);
-  return check_launch("igemm3_w16");
-}
-
-template <int BM, int BN, int S, int PP = 0>
-static int launch3_w8(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
-  SEDT_DESCRIBE("igemm3_w8_kernel<%d, %d, %d, %d>", BM, BN, S, PP);
-  constexpr size_t ring = (size_t)S * (BM + BN) * ROWB;
-  constexpr size_t ctile = (size_t)BM * (BN + 4) * sizeof(float);
-  constexpr size_t lds = ring > ctile ? ring : ctile;
-  static bool attr_set = false;
-  auto kern = igemm3_w8_kernel<BM, BN, S, PP>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("igemm3 w8: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  const int nwg = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), lds, st, p, a_bytes, b_bytes);
-  return check_launch("igemm3_w8");
-}
-
-#ifdef SEDT_DEV
-template <int BM, int BN, int S>
-static int launch3_br(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
-  SEDT_DESCRIBE("igemm3_br_kernel<%d, %d, %d>", BM, BN, S);
-  constexpr size_t ring = (size_t)S * BM * ROWB;
-  constexpr size_t ctile = (size_t)BM * (BN + 4) * sizeof(float);
-  constexpr size_t lds = ring > ctile ? ring : ctile;
-  static bool attr_set = false;
-  auto kern = igemm3_br_kernel<BM, BN, S>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("igemm3 br: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  const int nwg = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), lds, st, p, a_bytes, b_bytes);
-  return check_launch("igemm3_br");
-}
-#endif
-
 // Co-scheduled launch: the first nwg_main workgroups run the forward / dgrad GEMM p, the rest run pending weight-gradient
 // problems.  At batch 64 most GEMMs of the backward chain occupy 2 of the ~5 workgroup slots of a CU; weight gradients
 // are needed only by the optimizer, so their tiles ride in the spare slots of the chain's launches instead of taking
@@ -816,18 +751,6 @@ __global__ __launch_bounds__(256) void igemm3_co_kernel(const SedtIgemm p, const
   if ((int)blockIdx.x < nwg_main) igemm3_body<BM, BN, S>(p, a_bytes, b_bytes, blockIdx.x);
   else wgrad_group_run(g, (int)blockIdx.x - nwg_main);
 }
-
-// set by sedt_igemm_co (igemm.hip) around its sedt_igemm call: the weight-gradient group the next igemm3 launch takes along
-thread_local const WgradGroup* co_group = nullptr;
-thread_local bool co_taken = false;
-
-// dry run: igemm3_try resolves the kernel configuration of a problem without launching (sedt_igemm_group uses it)
-struct Igemm3Plan {
-  bool on, ok;
-  int bm, bn, s;
-  unsigned a_bytes, b_bytes;
-};
-thread_local Igemm3Plan plan3 = {false, false, 0, 0, 0, 0u, 0u};
 
 // several independent forward / dgrad problems of the 64x64 configuration (all with the same ring depth) in ONE launch (the q / k / v projections
 // of an attention block and their three dgrads are independent GEMMs of a few microseconds each)
@@ -862,197 +785,91 @@ __global__ __launch_bounds__(512) void igemm3_br_group_kernel(const IgemmGroup g
   while (i + 1 < g.n && (int)blockIdx.x >= g.blk0[i + 1]) ++i;
   igemm3_body<BM, BN, S, 8, 1, 1, 1>(g.p[i], g.a_bytes[i], g.b_bytes[i], (int)blockIdx.x - g.blk0[i]);
 }
-
-template <int BM, int BN, int S>
-static int launch3_br_group(const IgemmGroup& g, int nblk, hipStream_t st) {
-  constexpr size_t ring = (size_t)S * BM * ROWB;
-  constexpr size_t ctile = (size_t)BM * (BN + 4) * sizeof(float);
-  constexpr size_t lds = ring > ctile ? ring : ctile;
-  static bool attr_set = false;
-  auto kern = igemm3_br_group_kernel<BM, BN, S>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("igemm3 br group: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, st, g);
-  return check_launch("igemm3_br_group");
-}
 #endif
 
-template <int BM, int BN, int S>
-static int launch3_w8_group(const IgemmGroup& g, int nblk, hipStream_t st) {
-  constexpr size_t ring = (size_t)S * (BM + BN) * ROWB;
-  constexpr size_t ctile = (size_t)BM * (BN + 4) * sizeof(float);
-  constexpr size_t lds = ring > ctile ? ring : ctile;
-  static bool attr_set = false;
-  auto kern = igemm3_w8_group_kernel<BM, BN, S>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("igemm3 w8 group: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, st, g);
-  return check_launch("igemm3_w8_group");
+// ---------------------------------------------------------------------------- host side: the plan
+bool wgrad_plan(const SedtIgemm& p, LdsPlan* plan);          // wgrad3.hip: the weight-gradient half of lds_plan
+
+// B through registers (SedtIgemm.bfrag given; SEDT_IGEMM_BREG=1, so never in the product): what the fragment-major image must satisfy
+static bool breg_ok(const SedtIgemm& p) {
+  static const int breg = dev_int("SEDT_IGEMM_BREG", 0);
+  return breg && p.bfrag != nullptr && !p.f32ep && !p.awrap && (p.N % 32) == 0 && (p.ldb % 64) == 0 &&
+         (reinterpret_cast<uintptr_t>(p.bfrag) & 15) == 0 && (long)p.N * p.ldb * 2 < (1L << 31);
 }
 
-template <int BM, int BN, int S>
-static int launch3_co(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st, const WgradGroup& g) {
-  constexpr size_t ring = (size_t)S * (BM + BN) * ROWB;
-  constexpr size_t ctile = (size_t)BM * (BN + 4) * sizeof(float);
-  constexpr size_t wg = (size_t)2 * (64 * ROWB + 64 * 64 * 2);
-  constexpr size_t lds0 = ring > ctile ? ring : ctile;
-  constexpr size_t lds = lds0 > wg ? lds0 : wg;
-  static bool attr_set = false;
-  auto kern = igemm3_co_kernel<BM, BN, S>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("igemm3 co: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
+// The plan of one problem of the LDS-DMA GEMM family: envelope, tile rule, depth rule, program - a pure function of the argument block and
+// the context (the switches it reads are constants of the process).  false = outside the envelope: the general kernel (igemm.hip) takes it.
+bool lds_plan(const SedtIgemm& p, LdsContext ctx, LdsPlan* plan) {
+  if (p.trans) return wgrad_plan(p, plan);
+  const bool alone = ctx == LDS_SINGLE;      // the 8- and 16-wave programs and the 1-stage instance have no grouped / co-scheduled form
+  // ---- envelope
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  if ((p.out_f32 != 0) != (p.f32ep != 0) || p.splitk > 1 || p.act == SEDT_ACT_SIGMOID) return false;      // f32 C only with the f32 epilogue
+  if (p.f32ep && ((p.ldr & 3) || (p.ldm & 3) || !al16(p.res) || (!p.mask_bits && !al16(p.mask)))) return false;
+  if ((p.K & 7) || (p.N & 7) || (p.lda & 7) || (p.ldb & 7) || (p.ldc & 7)) return false;
+  if (!al16(p.A) || !al16(p.B) || !al16(p.C)) return false;
+  if (!p.f32ep && p.res && (!al16(p.res) || (p.ldr & 7))) return false;
+  if (!p.f32ep && p.mask && !p.mask_bits && (!al16(p.mask) || (p.ldm & 7))) return false;
+  if (p.conv && (p.Ci % BK2)) return false;
+  // bytes addressable through the A descriptor: every gathered pixel row + one K tile past its start
+  long a_rows = p.conv ? (long)((p.M + (long)p.Ho * p.Wo - 1) / ((long)p.Ho * p.Wo)) * p.Hi * p.Wi : (long)p.M;
+  long a_bytes = ((a_rows - 1) * p.lda + (p.awrap ? 2 * p.awrap : (p.conv ? p.Ci : p.K))) * 2;
+  if (p.awrap && 3 * p.awrap != (p.conv ? p.Ci : p.K)) return false;
+  long b_bytes = ((long)(p.N - 1) * p.ldb + p.K) * 2;
+  if (p.btap_on) {
+    if (!p.conv || p.KH * p.KW > 8) return false;
+    b_bytes = (long)p.N * p.ldb * 2;                 // (the tap table points anywhere inside a B row)
   }
-  const int nwg = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
-  hipLaunchKernelGGL(kern, dim3(nwg + g.blk0[g.n]), dim3(256), lds, st, p, a_bytes, b_bytes, nwg, g);
-  co_taken = true;
-  return check_launch("igemm3_co");
-}
+  if (p.omap && !p.conv) return false;
+  if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31) || a_bytes <= 0 || b_bytes <= 0) return false;
+  static const int v3 = dev_int("SEDT_IGEMM_V3", 1);
+  if (!v3) return false;
+  if (p.K % BK2) return false;
+  if (p.conv && (p.KH * p.KW > 32 || (p.transposed && (p.sh != p.sw || (p.lda % p.sh) != 0)))) return false;
+  if (!al16(p.scale) || !al16(p.bias)) return false;
+  // bit 31 of the B descriptor size = "the first workgroups prefetch the whole B operand" (igemm3_impl): on for every forward / dgrad problem -
+  // B is a weight there (same-box A/B in profiles/r06_ab_bpf.txt; SEDT_IGEMM_BPF=0 in the developer build)
+  static const int bpf = dev_int("SEDT_IGEMM_BPF", 1);
+  // bit 31 of the A descriptor size = "the first workgroups prefetch this program's own code" (igemm3_impl; SEDT_IGEMM_CPF=0 in the developer build;
+  // same-box A/B in profiles/r06_ab_bpf.txt)
+  static const int cpf = dev_int("SEDT_IGEMM_CPF", 1);
+  plan->a_bytes = (unsigned)a_bytes | (cpf ? 0x80000000u : 0u);
+  plan->b_bytes = (unsigned)b_bytes | (bpf ? 0x80000000u : 0u);
 
-template <int BM, int BN, int S>
-static int launch3(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
-  if (!plan3.on) SEDT_DESCRIBE("igemm3_kernel<%d, %d, %d>", BM, BN, S);
-  if (plan3.on) {
-    plan3.ok = true;
-    plan3.bm = BM; plan3.bn = BN; plan3.s = S;
-    plan3.a_bytes = a_bytes; plan3.b_bytes = b_bytes;
-    return 0;
+  // ---- tile rule
+  int bm = p.tile_m, bn = p.tile_n;
+  // measured (tools/tune_igemm.py on MI355X): occupancy beats prefetch depth at every SEDT shape - the 64x64 tile with a
+  // 2-stage ring (32 KB LDS, 5 workgroups per CU) wins or ties; SEDT_IGEMM_STAGES / tile_m override for experiments
+  if (bm == 0 || bn == 0) {
+    bm = 64; bn = 64;
+    const bool member = ctx == LDS_MEMBER;
+    // measured with the lean-issue kernel (tools/tune_igemm.py): the wider N tile (one A fragment feeds two MFMAs) wins
+    // once K is deep and enough tiles remain to fill the chip; everything else prefers the 64x64 tile's occupancy
+    // (with the 8-wave form of that tile the tile-count condition of the 4-wave kernel no longer applies)
+    // (a member of a grouped launch runs on the 64x64 program: worth it for the launch-bound decoder-sized problems)
+    static const int mink = dev_int("SEDT_IGEMM_BN128_MINK", 512);
+    static const int bn128t = dev_int("SEDT_IGEMM_BN128_MINTILES", 250);
+    // below 250 tiles of 64x128 the 64x64 tile covers more of the chip: the B = 32 configurations have M = 3968 rows, i.e. 124
+    // tiles of 64x128 at N = 256 (measured, tools/dev/sweep_c3.sh: C3 4.97 -> 4.88 ms, C5 8.71 -> 8.61 ms, C2 - exactly 256 tiles -
+    // unchanged; a threshold of 300 costs C2 0.2 %)
+    const long t128 = (long)((p.M + 63) / 64) * (p.N / 128);
+    if ((p.N % 128) == 0 && p.K >= mink && !(member && p.M <= 1024) && (t128 >= bn128t || p.M <= 1024)) bn = 128;
+    // the ping-pong 8-wave kernel makes the 128x128 tile (one workgroup per CU) pay where the K loop is long enough to
+    // amortise its exposed prologue / epilogue and the tiles still cover the chip: layer4 conv1 fwd / conv2 / conv3 dgrad
+    static const int bm128k = dev_int("SEDT_IGEMM_BM128_MINK", 2048);
+    static const int bm128t = dev_int("SEDT_IGEMM_BM128_MINTILES", 256);
+    if (bn == 128 && p.K >= bm128k && (long)((p.M + 127) / 128) * (p.N / 128) >= bm128t && !member) bm = 128;
+    // the wide outputs of layer4 (conv3 and the projection: N = 2048) with a short K (512 / 1024 = 8 / 16 K tiles) are prologue- and
+    // epilogue-dominated on 64x128 tiles (2048 of them at M = 8192): a 256x128 tile (85 flop per staged byte instead of 43, 512 tiles =
+    // two per CU) with the epilogue operands read late (SEDT_IGEMM_BM256=0/1 in the developer build)
+    static const int bm256 = dev_int("SEDT_IGEMM_BM256", 0);
+    if (bm256 && bn == 128 && bm == 64 && p.K >= 512 && p.K <= 1024 && (p.M % 256) == 0 && (long)(p.M / 256) * (p.N / 128) >= 512 &&
+        !member && !p.f32ep)
+      bm = 256;
   }
-  // riders inherit the launch's LDS allocation: only the 32 KB configuration keeps their occupancy (5 workgroups per CU)
-  if (co_group != nullptr && !co_taken && BM == 64 && BN == 64 && S == 2) return launch3_co<BM, BN, S>(p, a_bytes, b_bytes, st, *co_group);
-  constexpr size_t ring = (size_t)S * (BM + BN) * ROWB;
-  constexpr size_t ctile = (size_t)BM * (BN + 4) * sizeof(float);
-  constexpr size_t lds = ring > ctile ? ring : ctile;
-  static bool attr_set = false;
-  auto kern = igemm3_kernel<BM, BN, S>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("igemm3: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  const int nwg = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, st, p, a_bytes, b_bytes);
-  return check_launch("igemm3");
-}
 
-int igemm_lds_try(const SedtIgemm& p, hipStream_t st);   // below: envelope checks + tile choice, then igemm3_try
-bool igemm3_planning() { return plan3.on; }
-
-// 0 = launched as one grouped kernel, -1 = some problem does not resolve to the 64x64 2-stage kernel (nothing launched)
-int igemm3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM_GROUP");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!on || njobs < 2 || njobs > IG_MAXG) return -1;
-  IgemmGroup g;
-  g.n = njobs;
-  int blk = 0, S = 0, big = 0;
-  for (int i = 0; i < njobs; ++i) {
-    const SedtIgemm& p = jobs[i];
-    if (p.trans) return -1;
-    plan3 = {true, false, 0, 0, 0, 0u, 0u};
-    const int r = igemm_lds_try(p, st);
-    const Igemm3Plan got = plan3;
-    plan3.on = false;
-    if (r != 0 || !got.ok) return -1;
-    const bool b128 = got.bm == 128 && got.bn == 128 && got.s == 3;           // (requested by the caller's tile hint)
-    if (!b128 && (got.bm != 64 || got.bn != 64 || (got.s != 2 && got.s != 3))) return -1;
-    if (i == 0) big = b128;
-    if ((int)b128 != big) return -1;
-    if (i == 0) S = got.s;
-    if (got.s < S) S = got.s;               // mixed depths: the shallower ring serves every K
-    g.p[i] = p;
-    g.a_bytes[i] = got.a_bytes;
-    g.b_bytes[i] = got.b_bytes;
-    g.blk0[i] = blk;
-    blk += big ? ((p.N + 127) / 128) * ((p.M + 127) / 128) : ((p.N + 63) / 64) * ((p.M + 63) / 64);
-  }
-  g.blk0[njobs] = blk;
-#ifdef SEDT_DEV
-  if (big) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM_BREG");
-    bool br = e && atoi(e) != 0;
-    for (int i = 0; i < njobs && br; ++i) {
-      const SedtIgemm& p = jobs[i];
-      br = p.bfrag != nullptr && !p.f32ep && !p.awrap && (p.N % 32) == 0 && (p.ldb % 64) == 0 && (reinterpret_cast<uintptr_t>(p.bfrag) & 15) == 0 &&
-           (long)p.N * p.ldb * 2 < (1L << 31);
-    }
-    if (br) {
-      SEDT_DESCRIBE("igemm3_br_group_kernel<128, 128, 3>");
-      return launch3_br_group<128, 128, 3>(g, blk, st);
-    }
-  }
-#endif
-  if (big) SEDT_DESCRIBE("igemm3_w8_group_kernel<128, 128, 3>");
-  else SEDT_DESCRIBE("igemm3_group_kernel<%d>", S == 3 ? 3 : 2);
-  if (big) return launch3_w8_group<128, 128, 3>(g, blk, st);
-  if (S == 3) {
-    constexpr size_t lds = (size_t)3 * (64 + 64) * ROWB;
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm3_group_kernel<3>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        set_error("igemm3 group: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        return 1;
-      }
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(igemm3_group_kernel<3>, dim3(blk), dim3(256), lds, st, g);
-  } else {
-    constexpr size_t lds = (size_t)2 * (64 + 64) * ROWB;      // ring 32 KB >= the 17 KB epilogue tile
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm3_group_kernel<2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        set_error("igemm3 group: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        return 1;
-      }
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(igemm3_group_kernel<2>, dim3(blk), dim3(256), lds, st, g);
-  }
-  return check_launch("igemm3_group");
-}
-
-// -1 = outside the envelope
-int igemm3_try(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, int bm, int bn, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM_V3");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!on) return -1;
-  if (p.K % BK2) return -1;
-  if (p.conv && (p.KH * p.KW > 32 || (p.transposed && (p.sh != p.sw || (p.lda % p.sh) != 0)))) return -1;
-  if ((reinterpret_cast<uintptr_t>(p.scale) & 15) || (reinterpret_cast<uintptr_t>(p.bias) & 15)) return -1;
-  static int stages = -1;
-  if (stages < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM3_STAGES");
-    stages = e ? atoi(e) : 0;
-  }
+  // ---- depth rule
+  static const int stages = dev_int("SEDT_IGEMM3_STAGES", 0);
   int S = stages;
   if (S == 0) {
     // re-tuned after the 8-wave / lean-bookkeeping changes (full step, SEDT_IGEMM3_STAGES sweep: 2 everywhere 8881,
@@ -1062,191 +879,186 @@ int igemm3_try(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, int bm, i
     // convolution - few K tiles, fixed per-workgroup costs dominate - prefer the occupancy of the 2-stage ring)
     S = (p.K >= 5 * BK2 && !(p.N <= 64 && p.K <= 9 * BK2)) ? 3 : 2;
   }
-  static int nw_env = -1;
-  if (nw_env < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM3_NW");
-    nw_env = e ? atoi(e) : 0;
-  }
+  const int S23 = S >= 3 ? 3 : 2;
+
+  // ---- program
+  auto choose = [&](int prog, int bm_, int bn_, int s_, int pp_ = 0) {
+    plan->prog = prog; plan->bm = bm_; plan->bn = bn_; plan->s = s_; plan->pp = pp_;
+    return true;
+  };
   // measured (tools/tune_igemm.py, SEDT_IGEMM3_NW): the 64x128 tile runs 2-14 % faster with 8 waves (two groups splitting the
   // k16 steps) at every shape that selects it; 128x128 / 128x64 with 8 waves are experiment-only (SEDT_IGEMM3_NW=8)
-  static int pp_env = -1;
-  if (pp_env < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM3_PP");
-    pp_env = e ? atoi(e) : 1;
-  }
-  static int w4k = -1;          // experiment: below this K the 64x128 tile runs on the 4-wave kernel (32 MFMAs per wave and tile)
-  if (w4k < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM3_W4_BELOW_K");
-    w4k = e ? atoi(e) : 0;
-  }
-  const bool force4 = p.K < w4k;
+  static const int nw_env = dev_int("SEDT_IGEMM3_NW", 0);
+  static const int pp_env = dev_int("SEDT_IGEMM3_PP", 1);
+  static const int w4k = dev_int("SEDT_IGEMM3_W4_BELOW_K", 0);     // experiment: below this K the 64x128 tile runs on the 4-wave kernel (32 MFMAs per wave and tile)
+  const bool w8 = alone && nw_env != 4 && !(p.K < w4k);
   // exactly one 64x128 tile per CU and a long K: two 8-wave teams per workgroup, half of K each (SEDT_IGEMM3_W16=1)
-  static int w16 = -1, w16_mink = 0, w16_tiles = 320;
-  if (w16 < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM3_W16");        // same-box A/B on the C2 step: 5.688 -> 5.657 ms (29 launches, ~ -10 % each)
-    w16 = (e && e[0] == '0') ? 0 : 1;
-    e = sedt::dev_getenv("SEDT_IGEMM3_W16_TILES");
-    w16_tiles = e ? atoi(e) : 320;
-    e = sedt::dev_getenv("SEDT_IGEMM3_W16_MINK");
-    w16_mink = e ? atoi(e) : 512;            // (512 vs 1024: C2 5.61 vs 5.65 ms, C3 4.56 vs 4.58 - within the run-to-run spread)
-  }
-  if (w16 && !plan3.on && co_group == nullptr && bm == 64 && bn == 128 && S >= 3 && p.K >= w16_mink && (p.K / BK2) % 2 == 0) {
-    const long tiles = (long)((p.M + 63) / 64) * ((p.N + 127) / 128);
-    if (tiles <= w16_tiles) return launch3_w16<64, 128, 3>(p, a_bytes, b_bytes, st);
-  }
+  static const int w16 = dev_int("SEDT_IGEMM3_W16", 1);        // same-box A/B on the C2 step: 5.688 -> 5.657 ms (29 launches, ~ -10 % each)
+  static const int w16_tiles = dev_int("SEDT_IGEMM3_W16_TILES", 320);
+  static const int w16_mink = dev_int("SEDT_IGEMM3_W16_MINK", 512);      // (512 vs 1024: C2 5.61 vs 5.65 ms, C3 4.56 vs 4.58 - within the run-to-run spread)
+  const bool two_teams = alone && bm == 64 && S >= 3 && p.K >= w16_mink && (p.K / BK2) % 2 == 0;
+  if (w16 && two_teams && bn == 128 && (long)((p.M + 63) / 64) * ((p.N + 127) / 128) <= w16_tiles) return choose(LDS_IGEMM3_W16, 64, 128, 3);
   // the B = 32 configurations (M = 3968 rows) run on 64x64 tiles, 248 of them at N = 256 - one 4-wave workgroup per CU: the same
   // two-team form on that tile (same-box A/B: C3 4.655 -> 4.568 ms, C5 8.34 -> 8.27; one 8-wave team instead: no change)
-  static int small16 = -1;
-  if (small16 < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM3_SMALL16");
-    small16 = (e && e[0] == '0') ? 0 : 1;
+  static const int small16 = dev_int("SEDT_IGEMM3_SMALL16", 1);
+  if (small16 && two_teams && bn == 64 && (long)((p.M + 63) / 64) * ((p.N + 63) / 64) <= 320) return choose(LDS_IGEMM3_W16, 64, 64, 3);
+  // the 64x128 / 128x128 ping-pong problems with B through registers (developer build)
+  // (the ring holds A only and the epilogue's staging tile sets the LDS size, so a fourth / fifth stage is free: measured, 4 stages -4 % on
+  // these launches, 5 no better, profiles/r06_ab_breg.txt - the instances were removed again)
+  if (alone && bn == 128 && (bm == 64 || bm == 128) && breg_ok(p)) return choose(LDS_IGEMM3_BR, bm, 128, S23);
+  if (w8 && pp_env) {                            // 8 waves, ping-pong
+    if ((bm == 64 && bn == 128) || (bm == 128 && bn == 128) || (bm == 128 && bn == 64)) return choose(LDS_IGEMM3_W8, bm, bn, S23, 1);
+    if (bm == 256 && bn == 128 && S >= 3) return choose(LDS_IGEMM3_W8, 256, 128, 3, 1);
   }
-  if (small16 && !plan3.on && co_group == nullptr && bm == 64 && bn == 64 && S >= 3 && p.K >= w16_mink && (p.K / BK2) % 2 == 0) {
-    const long tiles = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-    if (tiles <= 320) return launch3_w16<64, 64, 3>(p, a_bytes, b_bytes, st);
-  }
-#ifdef SEDT_DEV
-  // B through registers (SedtIgemm.bfrag given; SEDT_IGEMM_BREG=1 in the developer build): the 64x128 / 128x128 ping-pong problems
-  static int breg = -1;
-  if (breg < 0) {
-    const char* e = sedt::dev_getenv("SEDT_IGEMM_BREG");
-    breg = e ? atoi(e) : 0;
-  }
-  if (breg && p.bfrag != nullptr && !plan3.on && co_group == nullptr && bn == 128 && (bm == 64 || bm == 128) && !p.f32ep && !p.awrap &&
-      (p.N % 32) == 0 && (p.ldb % 64) == 0 && (reinterpret_cast<uintptr_t>(p.bfrag) & 15) == 0 && (long)p.N * p.ldb * 2 < (1L << 31)) {
-    // (the ring holds A only and the epilogue's staging tile sets the LDS size, so a fourth / fifth stage is free: measured, 4 stages -4 % on
-    // these launches, 5 no better, profiles/r06_ab_breg.txt - the instances were removed again)
-    if (bm == 64) return S >= 3 ? launch3_br<64, 128, 3>(p, a_bytes, b_bytes, st) : launch3_br<64, 128, 2>(p, a_bytes, b_bytes, st);
-    return S >= 3 ? launch3_br<128, 128, 3>(p, a_bytes, b_bytes, st) : launch3_br<128, 128, 2>(p, a_bytes, b_bytes, st);
-  }
-#endif
-  if (!plan3.on && co_group == nullptr && nw_env != 4 && pp_env && !force4) {
-#define SEDT_PP(BM_, BN_)                                                                                   \
-  if (bm == BM_ && bn == BN_) {                                                                             \
-    return S >= 3 ? launch3_w8<BM_, BN_, 3, 1>(p, a_bytes, b_bytes, st) : launch3_w8<BM_, BN_, 2, 1>(p, a_bytes, b_bytes, st); \
-  }
-    SEDT_PP(64, 128)
-    SEDT_PP(128, 128)
-    SEDT_PP(128, 64)
-    if (bm == 256 && bn == 128 && S >= 3) return launch3_w8<256, 128, 3, 1>(p, a_bytes, b_bytes, st);
-#undef SEDT_PP
-  }
-  if (!plan3.on && co_group == nullptr && nw_env != 4 && !force4) {
-    if (bm == 64 && bn == 128) return S >= 3 ? launch3_w8<64, 128, 3>(p, a_bytes, b_bytes, st) : launch3_w8<64, 128, 2>(p, a_bytes, b_bytes, st);
-    if (nw_env == 8 && bm == 128 && bn == 128)
-      return S >= 3 ? launch3_w8<128, 128, 3>(p, a_bytes, b_bytes, st) : launch3_w8<128, 128, 2>(p, a_bytes, b_bytes, st);
-    if (nw_env == 8 && bm == 128 && bn == 64)
-      return S >= 3 ? launch3_w8<128, 64, 3>(p, a_bytes, b_bytes, st) : launch3_w8<128, 64, 2>(p, a_bytes, b_bytes, st);
-  }
-  if (bm == 64 && bn == 64 && p.K == BK2 && !plan3.on && co_group == nullptr) return launch3<64, 64, 1>(p, a_bytes, b_bytes, st);
-#define SEDT_L3(BM_, BN_)                                                      \
-  if (bm == BM_ && bn == BN_) {                                                \
-    if (S == 3) return launch3<BM_, BN_, 3>(p, a_bytes, b_bytes, st);          \
-    if (S == 4 && BM_ + BN_ <= 192) return launch3<BM_, BN_, 4>(p, a_bytes, b_bytes, st); \
-    return launch3<BM_, BN_, 2>(p, a_bytes, b_bytes, st);                      \
-  }
-  SEDT_L3(64, 64)
-  SEDT_L3(64, 128)
-  SEDT_L3(128, 64)
-  SEDT_L3(128, 128)
-#undef SEDT_L3
-  return -1;
+  if (w8 && ((bm == 64 && bn == 128) || (nw_env == 8 && bm == 128 && (bn == 128 || bn == 64)))) return choose(LDS_IGEMM3_W8, bm, bn, S23, 0);
+  if (alone && bm == 64 && bn == 64 && p.K == BK2) return choose(LDS_IGEMM3, 64, 64, 1);
+  if ((bm == 64 || bm == 128) && (bn == 64 || bn == 128)) return choose(LDS_IGEMM3, bm, bn, S == 3 ? 3 : (S == 4 && bm + bn <= 192) ? 4 : 2);
+  return false;
 }
 
-int wgrad_lds_try(const SedtIgemm& p, hipStream_t st);   // wgrad3.hip
+void lds_plan_name(const LdsPlan& pl, char* out, size_t cap) {
+  switch (pl.prog) {
+    case LDS_IGEMM3: snprintf(out, cap, "igemm3_kernel<%d, %d, %d>", pl.bm, pl.bn, pl.s); break;
+    case LDS_IGEMM3_W8: snprintf(out, cap, "igemm3_w8_kernel<%d, %d, %d, %d>", pl.bm, pl.bn, pl.s, pl.pp); break;
+    case LDS_IGEMM3_W16: snprintf(out, cap, "igemm3_w16_kernel<%d, %d, %d>", pl.bm, pl.bn, pl.s); break;
+    case LDS_IGEMM3_BR: snprintf(out, cap, "igemm3_br_kernel<%d, %d, %d>", pl.bm, pl.bn, pl.s); break;
+    case LDS_WGRAD3: snprintf(out, cap, "wgrad3_kernel<%d>", pl.bn); break;
+    case LDS_WGRAD4: snprintf(out, cap, "wgrad4_kernel<%d>", pl.s); break;
+    default: out[0] = 0;
+  }
+}
 
-// Envelope checks + tile rule of the LDS-DMA GEMM family, then the lean-issue kernel (igemm3_try).
-// Returns -1 when the problem is outside the envelope (the caller - sedt_igemm - then uses the general kernel of igemm.hip).
-int igemm_lds_try(const SedtIgemm& p, hipStream_t st) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (p.trans) {
-    return wgrad_lds_try(p, st);
+// ---------------------------------------------------------------------------- host side: the launch
+int lds_set_attr(const void* kern, size_t lds, const char* what) {
+  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) {
+    set_error("%s: raising the dynamic LDS limit to %zu B failed: %s", what, lds, hipGetErrorString(e));
+    return 1;
   }
-  if ((p.out_f32 != 0) != (p.f32ep != 0) || p.splitk > 1 || p.act == SEDT_ACT_SIGMOID) return -1;      // f32 C only with the f32 epilogue
-  if (p.f32ep && ((p.ldr & 3) || (p.ldm & 3) || (reinterpret_cast<uintptr_t>(p.res) & 15) ||
-                  (!p.mask_bits && (reinterpret_cast<uintptr_t>(p.mask) & 15)))) return -1;
-  if ((p.K & 7) || (p.N & 7) || (p.lda & 7) || (p.ldb & 7) || (p.ldc & 7)) return -1;
-  if (!al16(p.A) || !al16(p.B) || !al16(p.C)) return -1;
-  if (!p.f32ep && p.res && (!al16(p.res) || (p.ldr & 7))) return -1;
-  if (!p.f32ep && p.mask && !p.mask_bits && (!al16(p.mask) || (p.ldm & 7))) return -1;
-  if (p.conv && (p.Ci % BK2)) return -1;
-  // bytes addressable through the A descriptor: every gathered pixel row + one K tile past its start
-  long a_rows = p.conv ? (long)((p.M + (long)p.Ho * p.Wo - 1) / ((long)p.Ho * p.Wo)) * p.Hi * p.Wi : (long)p.M;
-  long a_bytes = ((a_rows - 1) * p.lda + (p.awrap ? 2 * p.awrap : (p.conv ? p.Ci : p.K))) * 2;
-  if (p.awrap && 3 * p.awrap != (p.conv ? p.Ci : p.K)) return -1;
-  long b_bytes = ((long)(p.N - 1) * p.ldb + p.K) * 2;
-  if (p.btap_on) {
-    if (!p.conv || p.KH * p.KW > 8) return -1;
-    b_bytes = (long)p.N * p.ldb * 2;                 // (the tap table points anywhere inside a B row)
+  return 0;
+}
+
+// LDS of an instance: its ring - S stages of `rows` 128-byte rows, per team - or the f32 staging tile(s) of the epilogue, which alias it
+constexpr size_t lds3(int BM, int BN, int S, int rows, int teams = 1) {
+  const size_t ring = (size_t)teams * S * rows * ROWB, ctile = (size_t)teams * teams * BM * (BN + 4) * sizeof(float);
+  return ring > ctile ? ring : ctile;
+}
+static int nwg3(const SedtIgemm& p, int BM, int BN) { return ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM); }
+
+template <int BM, int BN, int S>
+static int launch3(const LdsPlan& pl, const SedtIgemm& p, hipStream_t st, const WgradGroup* riders, bool* taken) {
+  const int nwg = nwg3(p, BM, BN);
+  // riders inherit the launch's LDS allocation: only the 32 KB configuration keeps their occupancy (5 workgroups per CU)
+  if (riders != nullptr && BM == 64 && BN == 64 && S == 2) {
+    constexpr size_t wg = (size_t)2 * (64 * ROWB + 64 * 64 * 2), lds = lds3(BM, BN, S, BM + BN) > wg ? lds3(BM, BN, S, BM + BN) : wg;
+    *taken = true;
+    return lds_launch_kernel<igemm3_co_kernel<BM, BN, S>>("igemm3_co", lds, dim3(nwg + riders->blk0[riders->n]), 256, st, p, pl.a_bytes,
+                                                          pl.b_bytes, nwg, *riders);
   }
-  if (p.omap && !p.conv) return -1;
-  if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31) || a_bytes <= 0 || b_bytes <= 0) return -1;
-  int bm = p.tile_m, bn = p.tile_n;
-  // measured (tools/tune_igemm.py on MI355X): occupancy beats prefetch depth at every SEDT shape - the 64x64 tile with a
-  // 2-stage ring (32 KB LDS, 5 workgroups per CU) wins or ties; SEDT_IGEMM_STAGES / tile_m override for experiments
-  if (bm == 0 || bn == 0) {
-    bm = 64; bn = 64;
-    // measured with the lean-issue kernel (tools/tune_igemm.py): the wider N tile (one A fragment feeds two MFMAs) wins
-    // once K is deep and enough tiles remain to fill the chip; everything else prefers the 64x64 tile's occupancy
-    // (with the 8-wave form of that tile - igemm3.hip - the tile-count condition of the 4-wave kernel no longer applies)
-    // (a grouped launch - igemm3_planning() - runs on the 64x64 program: worth it for the launch-bound decoder-sized problems)
-    static int mink = -1;
-    if (mink < 0) {
-      const char* e = sedt::dev_getenv("SEDT_IGEMM_BN128_MINK");
-      mink = e ? atoi(e) : 512;
-    }
-    static int bn128t = -1;
-    if (bn128t < 0) {
-      const char* e = sedt::dev_getenv("SEDT_IGEMM_BN128_MINTILES");
-      bn128t = e ? atoi(e) : 250;
-    }
-    // below 250 tiles of 64x128 the 64x64 tile covers more of the chip: the B = 32 configurations have M = 3968 rows, i.e. 124
-    // tiles of 64x128 at N = 256 (measured, tools/dev/sweep_c3.sh: C3 4.97 -> 4.88 ms, C5 8.71 -> 8.61 ms, C2 - exactly 256 tiles -
-    // unchanged; a threshold of 300 costs C2 0.2 %)
-    const long t128 = (long)((p.M + 63) / 64) * (p.N / 128);
-    if ((p.N % 128) == 0 && p.K >= mink && !(igemm3_planning() && p.M <= 1024) && (t128 >= bn128t || p.M <= 1024)) bn = 128;
-    // the ping-pong 8-wave kernel makes the 128x128 tile (one workgroup per CU) pay where the K loop is long enough to
-    // amortise its exposed prologue / epilogue and the tiles still cover the chip: layer4 conv1 fwd / conv2 / conv3 dgrad
-    static int bm128k = -1, bm128t = -1;
-    if (bm128k < 0) {
-      const char* e = sedt::dev_getenv("SEDT_IGEMM_BM128_MINK");
-      bm128k = e ? atoi(e) : 2048;
-      e = sedt::dev_getenv("SEDT_IGEMM_BM128_MINTILES");
-      bm128t = e ? atoi(e) : 256;
-    }
-    if (bn == 128 && p.K >= bm128k && (long)((p.M + 127) / 128) * (p.N / 128) >= bm128t && !igemm3_planning()) bm = 128;
-    // the wide outputs of layer4 (conv3 and the projection: N = 2048) with a short K (512 / 1024 = 8 / 16 K tiles) are prologue- and
-    // epilogue-dominated on 64x128 tiles (2048 of them at M = 8192): a 256x128 tile (85 flop per staged byte instead of 43, 512 tiles =
-    // two per CU) with the epilogue operands read late (SEDT_IGEMM_BM256=0/1 in the developer build)
-    static int bm256 = -1;
-    if (bm256 < 0) {
-      const char* e = sedt::dev_getenv("SEDT_IGEMM_BM256");
-      bm256 = e ? atoi(e) : 0;
-    }
-    if (bm256 && bn == 128 && bm == 64 && p.K >= 512 && p.K <= 1024 && (p.M % 256) == 0 && (long)(p.M / 256) * (p.N / 128) >= 512 &&
-        !igemm3_planning() && !p.f32ep)
-      bm = 256;
+  return lds_launch_kernel<igemm3_kernel<BM, BN, S>>("igemm3", lds3(BM, BN, S, BM + BN), dim3(nwg), 256, st, p, pl.a_bytes, pl.b_bytes);
+}
+
+// the one place that maps a plan to a kernel instance (the weight-gradient programs: to the function of their file that does)
+int launch_wgrad3(const LdsPlan& pl, const SedtIgemm& p, hipStream_t st);      // wgrad3.hip
+int launch_wgrad4(const LdsPlan& pl, const SedtIgemm& p, hipStream_t st);      // wgrad4.hip
+
+int lds_launch(const LdsPlan& pl, const SedtIgemm& p, hipStream_t st, const WgradGroup* riders, bool* taken) {
+  bool none;
+  if (!taken) taken = &none;
+  *taken = false;
+  if (pl.prog == LDS_WGRAD3) return launch_wgrad3(pl, p, st);
+  if (pl.prog == LDS_WGRAD4) return launch_wgrad4(pl, p, st);
+#define SEDT_INST(PROG_, BM_, BN_, S_, PP_, ...) \
+  if (pl.prog == PROG_ && pl.bm == BM_ && pl.bn == BN_ && pl.s == S_ && pl.pp == PP_) return __VA_ARGS__;
+#define SEDT_L3(BM_, BN_, S_) SEDT_INST(LDS_IGEMM3, BM_, BN_, S_, 0, launch3<BM_, BN_, S_>(pl, p, st, riders, taken))
+#define SEDT_W8(BM_, BN_, S_, PP_)                                                                                                    \
+  SEDT_INST(LDS_IGEMM3_W8, BM_, BN_, S_, PP_, lds_launch_kernel<igemm3_w8_kernel<BM_, BN_, S_, PP_>>(                                  \
+      "igemm3_w8", lds3(BM_, BN_, S_, BM_ + BN_), dim3(nwg3(p, BM_, BN_)), 512, st, p, pl.a_bytes, pl.b_bytes))
+#define SEDT_W16(BM_, BN_)                                                                                                            \
+  SEDT_INST(LDS_IGEMM3_W16, BM_, BN_, 3, 0, lds_launch_kernel<igemm3_w16_kernel<BM_, BN_, 3>>(                                         \
+      "igemm3_w16", lds3(BM_, BN_, 3, BM_ + BN_, 2), dim3(nwg3(p, BM_, BN_)), 1024, st, p, pl.a_bytes, pl.b_bytes))
+#define SEDT_BR(BM_, S_)                                                                                                              \
+  SEDT_INST(LDS_IGEMM3_BR, BM_, 128, S_, 0, lds_launch_kernel<igemm3_br_kernel<BM_, 128, S_>>(                                         \
+      "igemm3_br", lds3(BM_, 128, S_, BM_), dim3(nwg3(p, BM_, 128)), 512, st, p, pl.a_bytes, pl.b_bytes))
+  SEDT_L3(64, 64, 1)
+  SEDT_L3(64, 64, 2) SEDT_L3(64, 64, 3) SEDT_L3(64, 64, 4)
+  SEDT_L3(64, 128, 2) SEDT_L3(64, 128, 3) SEDT_L3(64, 128, 4)
+  SEDT_L3(128, 64, 2) SEDT_L3(128, 64, 3) SEDT_L3(128, 64, 4)
+  SEDT_L3(128, 128, 2) SEDT_L3(128, 128, 3) SEDT_L3(128, 128, 4)      // (4 stages are planned only where BM + BN <= 192; the instance stays compiled)
+  SEDT_W8(64, 128, 2, 1) SEDT_W8(64, 128, 3, 1) SEDT_W8(128, 128, 2, 1) SEDT_W8(128, 128, 3, 1) SEDT_W8(128, 64, 2, 1) SEDT_W8(128, 64, 3, 1)
+  SEDT_W8(256, 128, 3, 1)
+  SEDT_W8(64, 128, 2, 0) SEDT_W8(64, 128, 3, 0) SEDT_W8(128, 128, 2, 0) SEDT_W8(128, 128, 3, 0) SEDT_W8(128, 64, 2, 0) SEDT_W8(128, 64, 3, 0)
+  SEDT_W16(64, 128) SEDT_W16(64, 64)
+#ifdef SEDT_DEV
+  SEDT_BR(64, 2) SEDT_BR(64, 3) SEDT_BR(128, 2) SEDT_BR(128, 3)
+#endif
+#undef SEDT_BR
+#undef SEDT_W16
+#undef SEDT_W8
+#undef SEDT_L3
+#undef SEDT_INST
+  set_error("lds_launch: no instance for program %d, tile %d x %d, %d stages, pp %d", pl.prog, pl.bm, pl.bn, pl.s, pl.pp);
+  return 1;
+}
+
+// ---------------------------------------------------------------------------- grouped launches (sedt_igemm_group)
+// The plan of a group: every member plans as LDS_MEMBER to ONE configuration - the 64x64 tile with a 2- or 3-stage ring, or (by the
+// caller's tile hint) 128x128 with 3 stages, which runs on the ping-pong program.  Fills g; false = the members run one launch each.
+struct IgemmGroupPlan {
+  bool big, br;       // 128x128 ping-pong; (developer build) B through registers
+  int s, nblk;
+};
+static bool igemm3_group_plan(const SedtIgemm* jobs, int njobs, IgemmGroup* g, IgemmGroupPlan* gp) {
+  static const int on = dev_int("SEDT_IGEMM_GROUP", 1);
+  if (!on || njobs < 2 || njobs > IG_MAXG) return false;
+  g->n = njobs;
+  int blk = 0, S = 0;
+  bool big = false, br = true;
+  for (int i = 0; i < njobs; ++i) {
+    const SedtIgemm& p = jobs[i];
+    LdsPlan pl;
+    if (p.trans || !lds_plan(p, LDS_MEMBER, &pl)) return false;
+    const bool b128 = pl.bm == 128 && pl.bn == 128 && pl.s == 3;           // (requested by the caller's tile hint)
+    if (!b128 && (pl.bm != 64 || pl.bn != 64 || (pl.s != 2 && pl.s != 3))) return false;
+    if (i == 0) big = b128;
+    if (b128 != big) return false;
+    if (i == 0 || pl.s < S) S = pl.s;         // mixed depths: the shallower ring serves every K
+    g->p[i] = p;
+    g->a_bytes[i] = pl.a_bytes;
+    g->b_bytes[i] = pl.b_bytes;
+    g->blk0[i] = blk;
+    blk += big ? nwg3(p, 128, 128) : nwg3(p, 64, 64);
+    br = br && breg_ok(p);
   }
-  {   // the lean-issue kernel takes the common cases
-    // bit 31 of the B descriptor size = "the first workgroups prefetch the whole B operand" (igemm3_impl): on for every forward / dgrad problem -
-    // B is a weight there (same-box A/B in profiles/r06_ab_bpf.txt; SEDT_IGEMM_BPF=0 in the developer build)
-    static int bpf = -1;
-    if (bpf < 0) {
-      const char* e = sedt::dev_getenv("SEDT_IGEMM_BPF");
-      bpf = e ? atoi(e) : 1;
-    }
-    // bit 31 of the A descriptor size = "the first workgroups prefetch this program's own code" (igemm3_impl; SEDT_IGEMM_CPF=0 in the developer build;
-    // same-box A/B in profiles/r06_ab_bpf.txt)
-    static int cpf = -1;
-    if (cpf < 0) {
-      const char* e = sedt::dev_getenv("SEDT_IGEMM_CPF");
-      cpf = e ? atoi(e) : 1;
-    }
-    int r3 = igemm3_try(p, (unsigned)a_bytes | (cpf ? 0x80000000u : 0u), (unsigned)b_bytes | (bpf ? 0x80000000u : 0u), bm, bn, st);
-    if (r3 >= 0) return r3;
-    if (igemm3_planning()) return -1;      // dry run (sedt_igemm_group): never launch from here
-  }
-  return -1;                             // outside the lean-issue envelope: the general kernel (igemm.hip) takes it
+  g->blk0[njobs] = blk;
+  *gp = {big, big && br, S, blk};
+  return true;
+}
+
+static const char* igemm3_group_name(const IgemmGroupPlan& gp) {
+  if (gp.big) return gp.br ? "igemm3_br_group_kernel<128, 128, 3>" : "igemm3_w8_group_kernel<128, 128, 3>";
+  return gp.s == 3 ? "igemm3_group_kernel<3>" : "igemm3_group_kernel<2>";
+}
+
+// 0 = launched as one grouped kernel, -1 = the problems do not plan to one configuration (nothing launched)
+int igemm3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st) {
+  IgemmGroup g;
+  IgemmGroupPlan gp;
+  if (!igemm3_group_plan(jobs, njobs, &g, &gp)) return -1;
+  const dim3 grid(gp.nblk);
+#ifdef SEDT_DEV
+  if (gp.br) return lds_launch_kernel<igemm3_br_group_kernel<128, 128, 3>>("igemm3_br_group", lds3(128, 128, 3, 128), grid, 512, st, g);
+#endif
+  if (gp.big) return lds_launch_kernel<igemm3_w8_group_kernel<128, 128, 3>>("igemm3_w8_group", lds3(128, 128, 3, 256), grid, 512, st, g);
+  if (gp.s == 3) return lds_launch_kernel<igemm3_group_kernel<3>>("igemm3_group", lds3(64, 64, 3, 128), grid, 256, st, g);
+  return lds_launch_kernel<igemm3_group_kernel<2>>("igemm3_group", lds3(64, 64, 2, 128), grid, 256, st, g);      // ring 32 KB >= the 17 KB epilogue tile
+}
+
+// the instance igemm3_group_try would launch ("" = one launch each)
+void igemm3_group_describe(const SedtIgemm* jobs, int njobs, char* out, size_t cap) {
+  IgemmGroup g;
+  IgemmGroupPlan gp;
+  snprintf(out, cap, "%s", igemm3_group_plan(jobs, njobs, &g, &gp) ? igemm3_group_name(gp) : "");
 }
 
 }  // namespace sedt

@@ -39,4 +39,36 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
 }
 
+// ---- host side.  Which kernel instance runs a problem is decided by ONE pure function of the argument block (lds_plan, igemm3.hip): no HIP
+// call, no state.  lds_launch (igemm3.hip) is the only place that turns a plan into a launch; the label sedt_igemm_describe prints is
+// the plan's name.
+enum LdsProgram { LDS_IGEMM3, LDS_IGEMM3_W8, LDS_IGEMM3_W16, LDS_WGRAD3, LDS_WGRAD4, LDS_IGEMM3_BR /* developer builds only */ };
+// what the launch is: a problem of its own, one member of a grouped launch (sedt_igemm_group), or the main GEMM of a launch that takes
+// weight-gradient riders along (sedt_igemm_co).  Members and carriers run on the 4-wave program igemm3_kernel - the only one with
+// grouped / co-scheduled forms -, WHETHER OR NOT the launch then carries the riders (only its 64x64 2-stage instance can)
+enum LdsContext { LDS_SINGLE, LDS_MEMBER, LDS_CARRIER };
+struct LdsPlan {
+  int prog;                     // LdsProgram
+  int bm, bn, s, pp;            // tile, ring depth, igemm3_w8's PP
+  unsigned a_bytes, b_bytes;    // buffer-descriptor sizes (forward / dgrad: bit 31 = the prefetch bits, see lds_plan)
+};
+struct WgradGroup;
+bool lds_plan(const SedtIgemm& p, LdsContext ctx, LdsPlan* plan);      // false = outside the family's envelope
+void lds_plan_name(const LdsPlan& plan, char* out, size_t cap);       // the instance as a profiler prints it
+// *taken = the launch carried `riders`
+int lds_launch(const LdsPlan& plan, const SedtIgemm& p, hipStream_t st, const WgradGroup* riders = nullptr, bool* taken = nullptr);
+
+// every launch of the family: the dynamic-LDS attribute once per kernel instance, then the launch
+int lds_set_attr(const void* kern, size_t lds, const char* what);      // igemm3.hip
+template <auto Kern, typename... Args>
+int lds_launch_kernel(const char* what, size_t lds, dim3 grid, int threads, hipStream_t st, const Args&... args) {
+  static bool attr_set = false;  // idempotent; a benign race sets it twice
+  if (!attr_set) {
+    if (lds_set_attr(reinterpret_cast<const void*>(Kern), lds, what)) return 1;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(Kern, grid, dim3(threads), lds, st, args...);
+  return check_launch(what);
+}
+
 }  // namespace sedt

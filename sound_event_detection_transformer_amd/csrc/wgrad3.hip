@@ -22,172 +22,124 @@ __global__ __launch_bounds__(256) void wgrad3_kernel(const SedtIgemm p, const un
 
 __global__ __launch_bounds__(256) void wgrad3_group_kernel(const WgradGroup g) { wgrad_group_run(g, blockIdx.x); }
 
-template <int BN>
-static int launch_wgrad3(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
-  SEDT_DESCRIBE("wgrad3_kernel<%d>", BN);
-  constexpr size_t lds = (size_t)2 * (64 * ROWB + 64 * BN * 2);
-  static bool attr_set = false;
-  auto kern = wgrad3_kernel<BN>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("wgrad3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  const int nwg = ((p.N + BN - 1) / BN) * ((p.M + 63) / 64);
-  static int force = -2;
-  if (force == -2) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD_NMAJOR");
-    force = e ? atoi(e) : -1;
-  }
-  const int nmajor = force >= 0 ? force : (p.N > p.M ? 1 : 0);
-  hipLaunchKernelGGL(kern, dim3(nwg, p.splitk > 1 ? p.splitk : 1), dim3(256), lds, st, p, a_bytes, b_bytes, nmajor);
-  return check_launch("wgrad3");
-}
+// ---------------------------------------------------------------------------- host side (the plan and the launcher: igemm3.hip)
+bool wgrad4_ok(const SedtIgemm& p);                                        // wgrad4.hip: 128x128 / 256x128 ping-pong kernel
+int wgrad4_tile_m(int M, int N);
+int wgrad4_stages();
+int launch_wgrad4_group(WgradGroup& g, hipStream_t st);
 
 static bool wgrad3_conv_ok(const SedtIgemm& p) {
   return !(p.conv && ((64 % p.Wo) != 0 || p.Ho * p.Wo < 64 || p.Ho < 64 / p.Wo));
 }
 
-int wgrad_lds_envelope(const SedtIgemm& p, long* a_bytes, long* b_bytes);   // below
-bool wgrad4_ok(const SedtIgemm& p);                                        // wgrad4.hip: 128x128 ping-pong kernel
-int launch_wgrad4(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st);
-int launch_wgrad4_group(WgradGroup& g, hipStream_t st);
-
-// 0 = launched, -1 = some problem is outside the lean kernel's envelope (caller launches them one by one)
-int wgrad3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD_GROUP");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!on || njobs < 1) return -1;
-  long ab[WG_MAXG], bb[WG_MAXG];
-  for (int base = 0; base < njobs; base += WG_MAXG) {       // validate everything before launching anything
-    const int n = std::min(WG_MAXG, njobs - base);
-    for (int i = 0; i < n; ++i) {
-      const SedtIgemm& p = jobs[base + i];
-      if (!p.trans || wgrad_lds_envelope(p, &ab[i], &bb[i]) != 0 || !wgrad3_conv_ok(p)) return -1;
-    }
-  }
-  static bool attr_set = false;
-  constexpr size_t lds = (size_t)2 * (64 * ROWB + 64 * 64 * 2);
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) {
-      set_error("wgrad3 group: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 1;
-    }
-    attr_set = true;
-  }
-  for (int base = 0; base < njobs; base += WG_MAXG) {
-    WgradGroup g, gw;                 // the 64x64 program, and the large problems that take the 128x128 ping-pong kernel
-    g.n = gw.n = 0;
-    const int n = std::min(WG_MAXG, njobs - base);
-    int blk = 0;
-    for (int j = 0; j < n; ++j) {
-      const SedtIgemm& p = jobs[base + j];
-      long a, b;
-      wgrad_lds_envelope(p, &a, &b);
-      if (wgrad4_ok(p)) {
-        const int i = gw.n++;
-        gw.p[i] = p;
-        gw.a_bytes[i] = (unsigned)a;
-        gw.b_bytes[i] = (unsigned)b;
-        continue;
-      }
-      const int i = g.n++;
-      g.p[i] = p;
-      g.a_bytes[i] = (unsigned)a;
-      g.b_bytes[i] = (unsigned)b;
-      g.nwg[i] = ((p.N + 63) / 64) * ((p.M + 63) / 64);
-      g.nmajor[i] = (p.N > p.M ? 1 : 0) + ((p.splitk >= 8 && p.splitk % 8 == 0) ? 2 : 0);
-      g.blk0[i] = blk;
-      blk += (g.nwg[i] * (p.splitk > 1 ? p.splitk : 1) + 7) / 8 * 8;      // ranges start on multiples of 8 (XCD = id & 7)
-    }
-    if (gw.n > 0)
-      if (int r = launch_wgrad4_group(gw, st)) return r;
-    if (g.n > 0) {
-      g.blk0[g.n] = blk;
-      hipLaunchKernelGGL(wgrad3_group_kernel, dim3(blk), dim3(256), lds, st, g);
-      if (int r = check_launch("wgrad3_group")) return r;
-    }
-  }
-  return 0;
-}
-
-// fills g from up to WG_MAXG problems; -1 if one of them is outside the lean kernel's envelope
-int wgrad3_group_build(const SedtIgemm* jobs, int njobs, WgradGroup* g) {
-  if (njobs < 1 || njobs > WG_MAXG) return -1;
-  g->n = njobs;
-  int blk = 0;
-  for (int i = 0; i < njobs; ++i) {
-    const SedtIgemm& p = jobs[i];
-    long ab, bb;
-    if (!p.trans || wgrad_lds_envelope(p, &ab, &bb) != 0 || !wgrad3_conv_ok(p)) return -1;
-    g->p[i] = p;
-    g->a_bytes[i] = (unsigned)ab;
-    g->b_bytes[i] = (unsigned)bb;
-    g->nwg[i] = ((p.N + 63) / 64) * ((p.M + 63) / 64);
-    g->nmajor[i] = p.N > p.M ? 1 : 0;            // (riders of a co-scheduled launch do not start on an XCD boundary: no K-slice map)
-    g->blk0[i] = blk;
-    blk += g->nwg[i] * (p.splitk > 1 ? p.splitk : 1);
-  }
-  g->blk0[njobs] = blk;
-  return 0;
-}
-
-// -1 = outside the envelope (caller continues with wgrad2)
-int wgrad3_try(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
-  static int on = -1, wide = -1;
-  if (on < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD_V3");
-    on = (e && e[0] == '0') ? 0 : 1;
-    const char* w = sedt::dev_getenv("SEDT_WGRAD_WIDE");
-    wide = w ? atoi(w) : -1;
-  }
-  if (!on) return -1;
-  if (!wgrad3_conv_ok(p)) return -1;
-  if (wgrad4_ok(p)) return launch_wgrad4(p, a_bytes, b_bytes, st);
-  int bn = 64;
-  if (wide == 1) {   // measured on the full step: the wide tile does not pay (fewer, longer workgroups); opt-in only
-    // a 16-byte chunk never straddles a tap (Ci % 8 == 0), so the wide tile needs nothing beyond N % 128 == 0
-    if ((p.N % 128) == 0) bn = 128;
-  }
-  if (wide == 0) bn = 64;
-  return bn == 128 ? launch_wgrad3<128>(p, a_bytes, b_bytes, st) : launch_wgrad3<64>(p, a_bytes, b_bytes, st);
-}
-
-// 0 when the problem fits the LDS-DMA weight-gradient kernels (wgrad3 / wgrad4); fills the buffer-descriptor sizes
-int wgrad_lds_envelope(const SedtIgemm& p, long* a_bytes_out, long* b_bytes_out) {
+// true when the problem fits the LDS-DMA weight-gradient kernels (wgrad3 / wgrad4); fills the buffer-descriptor sizes
+static bool wgrad_lds_envelope(const SedtIgemm& p, unsigned* a_bytes_out, unsigned* b_bytes_out) {
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (p.scale || p.bias || p.res || p.mask || p.act != SEDT_ACT_NONE || p.drop_p > 0.f || p.alpha != 1.f) return -1;
-  if (p.splitk <= 1 && !p.out_f32) return -1;
-  if (p.splitk > 1 && !p.slab) return -1;
-  if ((p.M & 7) || (p.N & 7) || (p.lda & 7) || (p.ldb & 7)) return -1;
-  if (!al16(p.A) || !al16(p.B)) return -1;
-  if (p.conv && ((p.Ci & 7) || p.transposed)) return -1;
+  if (p.scale || p.bias || p.res || p.mask || p.act != SEDT_ACT_NONE || p.drop_p > 0.f || p.alpha != 1.f) return false;
+  if (p.splitk <= 1 && !p.out_f32) return false;
+  if (p.splitk > 1 && !p.slab) return false;
+  if ((p.M & 7) || (p.N & 7) || (p.lda & 7) || (p.ldb & 7)) return false;
+  if (!al16(p.A) || !al16(p.B)) return false;
+  if (p.conv && ((p.Ci & 7) || p.transposed)) return false;
   long a_bytes = ((long)(p.K - 1) * p.lda + p.M) * 2;
   long b_rows = p.conv ? (long)((p.K + (long)p.Ho * p.Wo - 1) / ((long)p.Ho * p.Wo)) * p.Hi * p.Wi : (long)p.K;
   long b_bytes = ((b_rows - 1) * p.ldb + (p.conv ? p.Ci : p.N)) * 2;
-  if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31) || a_bytes <= 0 || b_bytes <= 0) return -1;
-  *a_bytes_out = a_bytes;
-  *b_bytes_out = b_bytes;
+  if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31) || a_bytes <= 0 || b_bytes <= 0) return false;
+  *a_bytes_out = (unsigned)a_bytes;
+  *b_bytes_out = (unsigned)b_bytes;
+  return true;
+}
+
+// the weight-gradient half of lds_plan: envelope, then wgrad4 for the large problems, else wgrad3.  false = outside the envelope (the
+// general kernel takes it)
+bool wgrad_plan(const SedtIgemm& p, LdsPlan* plan) {
+  static const int v3 = dev_int("SEDT_WGRAD_V3", 1), wide = dev_int("SEDT_WGRAD_WIDE", -1);
+  if (!wgrad_lds_envelope(p, &plan->a_bytes, &plan->b_bytes) || !v3 || !wgrad3_conv_ok(p)) return false;
+  plan->pp = 0;
+  if (wgrad4_ok(p)) {
+    plan->prog = LDS_WGRAD4; plan->bm = wgrad4_tile_m(p.M, p.N); plan->bn = 128; plan->s = wgrad4_stages();
+    return true;
+  }
+  // measured on the full step: the wide tile does not pay (fewer, longer workgroups); opt-in only (SEDT_WGRAD_WIDE=1)
+  // a 16-byte chunk never straddles a tap (Ci % 8 == 0), so the wide tile needs nothing beyond N % 128 == 0
+  plan->prog = LDS_WGRAD3; plan->bm = 64; plan->bn = (wide == 1 && (p.N % 128) == 0) ? 128 : 64; plan->s = 2;
+  return true;
+}
+
+template <int BN>
+static int launch_wgrad3_bn(const LdsPlan& pl, const SedtIgemm& p, hipStream_t st) {
+  constexpr size_t lds = (size_t)2 * (64 * ROWB + 64 * BN * 2);
+  const int nwg = ((p.N + BN - 1) / BN) * ((p.M + 63) / 64);
+  static const int force = dev_int("SEDT_WGRAD_NMAJOR", -1);
+  const int nmajor = force >= 0 ? force : (p.N > p.M ? 1 : 0);
+  return lds_launch_kernel<wgrad3_kernel<BN>>("wgrad3", lds, dim3(nwg, p.splitk > 1 ? p.splitk : 1), 256, st, p, pl.a_bytes, pl.b_bytes, nmajor);
+}
+int launch_wgrad3(const LdsPlan& pl, const SedtIgemm& p, hipStream_t st) {
+  return pl.bn == 128 ? launch_wgrad3_bn<128>(pl, p, st) : launch_wgrad3_bn<64>(pl, p, st);
+}
+
+// ---- grouped launches (sedt_wgrad_group) and riders (sedt_igemm_co)
+// the kernel of sedt_wgrad_group that takes a problem: 4 = the 256/128x128 group (wgrad4), 3 = the 64x64 group, 0 = neither.  The label
+// sedt_igemm_describe(grouped = 1) prints is this class
+// (wgrad3_conv_ok is not part of it: a problem that fails it sends its whole group to single launches, yet is still labelled with a group kernel)
+int wgrad_group_class(const SedtIgemm& p, unsigned* a_bytes, unsigned* b_bytes) {
+  if (!p.trans || !wgrad_lds_envelope(p, a_bytes, b_bytes)) return 0;
+  return wgrad4_ok(p) ? 4 : 3;
+}
+
+// Fills g, the group of the 64x64 program, from up to WG_MAXG problems; false = one of them is outside the lean kernel's envelope.
+// riders = false (sedt_wgrad_group): the problems of class 4 go to g4 (launch_wgrad4_group completes it); problem ranges start on
+//   multiples of 8 workgroups (XCD = id & 7), and a split factor that is a multiple of 8 takes the K-slice map (bit 1 of nmajor).
+// riders = true (sedt_igemm_co): every problem rides on the 64x64 program; riders of a co-scheduled launch do not start on an XCD
+//   boundary: no padding, no K-slice map.
+static bool wgrad_group_fill(const SedtIgemm* jobs, int njobs, bool riders, WgradGroup* g, WgradGroup* g4) {
+  g->n = 0;
+  if (g4) g4->n = 0;
+  int blk = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const SedtIgemm& p = jobs[j];
+    unsigned a, b;
+    const int cls = wgrad_group_class(p, &a, &b);
+    if (cls == 0 || !wgrad3_conv_ok(p)) return false;
+    WgradGroup* t = (cls == 4 && !riders) ? g4 : g;
+    const int i = t->n++;
+    t->p[i] = p;
+    t->a_bytes[i] = a;
+    t->b_bytes[i] = b;
+    if (t != g) continue;
+    const int sk = p.splitk > 1 ? p.splitk : 1;
+    g->nwg[i] = ((p.N + 63) / 64) * ((p.M + 63) / 64);
+    g->nmajor[i] = (p.N > p.M ? 1 : 0) + ((!riders && sk >= 8 && sk % 8 == 0) ? 2 : 0);
+    g->blk0[i] = blk;
+    blk += riders ? g->nwg[i] * sk : (g->nwg[i] * sk + 7) / 8 * 8;
+  }
+  g->blk0[g->n] = blk;
+  return true;
+}
+
+// 0 = launched, -1 = some problem is outside the lean kernel's envelope (caller launches them one by one)
+int wgrad3_group_try(const SedtIgemm* jobs, int njobs, hipStream_t st) {
+  static const int on = dev_int("SEDT_WGRAD_GROUP", 1);
+  if (!on || njobs < 1) return -1;
+  for (int i = 0; i < njobs; ++i) {       // validate everything before launching anything
+    unsigned a, b;
+    if (wgrad_group_class(jobs[i], &a, &b) == 0 || !wgrad3_conv_ok(jobs[i])) return -1;
+  }
+  constexpr size_t lds = (size_t)2 * (64 * ROWB + 64 * 64 * 2);
+  for (int base = 0; base < njobs; base += WG_MAXG) {
+    WgradGroup g, g4;                 // the 64x64 program, and the large problems that take the 128x128 ping-pong kernel
+    wgrad_group_fill(jobs + base, std::min(WG_MAXG, njobs - base), false, &g, &g4);
+    if (g4.n > 0)
+      if (int r = launch_wgrad4_group(g4, st)) return r;
+    if (g.n > 0)
+      if (int r = lds_launch_kernel<wgrad3_group_kernel>("wgrad3_group", lds, dim3(g.blk0[g.n]), 256, st, g)) return r;
+  }
   return 0;
 }
 
-// returns -1 when the problem is outside the envelope (the caller then uses the general v1 kernel)
-int wgrad_lds_try(const SedtIgemm& p, hipStream_t st) {
-  long a_bytes, b_bytes;
-  if (wgrad_lds_envelope(p, &a_bytes, &b_bytes) != 0) return -1;
-  {   // the lean-issue kernel takes the common cases
-    int r3 = wgrad3_try(p, (unsigned)a_bytes, (unsigned)b_bytes, st);
-    if (r3 >= 0) return r3;
-  }
-  return -1;
+// the riders of a co-scheduled launch: fills g from up to WG_MAXG problems; -1 if one of them is outside the lean kernel's envelope
+int wgrad3_group_build(const SedtIgemm* jobs, int njobs, WgradGroup* g) {
+  return (njobs >= 1 && njobs <= WG_MAXG && wgrad_group_fill(jobs, njobs, true, g, nullptr)) ? 0 : -1;
 }
 
 }  // namespace sedt

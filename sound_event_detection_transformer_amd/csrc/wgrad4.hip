@@ -353,56 +353,36 @@ __global__ __launch_bounds__(512) void wgrad4_group_kernel(const WgradGroup g) {
   wgrad4_body<S>(g.p[i], g.a_bytes[i], g.b_bytes[i], g.nmajor[i], local % nwg, local / nwg);
 }
 
+// ---------------------------------------------------------------------------- host side (the plan and the launcher: igemm3.hip)
 // ring of S stages x 32 KB (96 / 128 KB) >= the 128 x 132 f32 epilogue tile (66 KB).  SEDT_WGRAD4_STAGES picks the depth.
-static int wg4_stages() {
-  static int s = -1;
-  if (s < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD4_STAGES");
-    s = (e && atoi(e) == 3) ? 3 : (e && atoi(e) == 4) ? 4 : 3;
-  }
+int wgrad4_stages() {
+  static const int s = dev_int("SEDT_WGRAD4_STAGES", 3) == 4 ? 4 : 3;
   return s;
 }
 // rows of a tile for a problem with M output rows (Cout): the 256 x 128 tile where M allows it (SEDT_WGRAD4_BM=128: never).
 // Same-box A/B on the C2 step (tools/dev/ab_wgrad4.sh, ms/step): 128-row tiles 5.85-5.86 at every split target; 256-row tiles
 // with split-K target 32 / 48 / 64 / 80 / 128 / 192 tiles: 5.79 / 5.71 / 5.67 / 5.74 / 5.81 / 5.96
 int wgrad4_tile_m(int M, int N) {
-  static int bm = -1, min_tiles = 1;
-  if (bm < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD4_BM");
-    bm = (e && atoi(e) == 128) ? 128 : 256;
-    e = sedt::dev_getenv("SEDT_WGRAD4_WIDE_MIN");               // experiment: the 256-row tile only for problems with at least this many of them
-    min_tiles = e ? atoi(e) : 1;
-  }
+  static const int bm = dev_int("SEDT_WGRAD4_BM", 256) == 128 ? 128 : 256;
+  static const int min_tiles = dev_int("SEDT_WGRAD4_WIDE_MIN", 1);      // experiment: the 256-row tile only for problems with at least this many of them
   return (bm == 256 && M % 256 == 0 && (long)(M / 256) * (N / 128) >= min_tiles) ? 256 : 128;
 }
 static size_t wg4_lds() {
-  const size_t narrow = (size_t)wg4_stages() * 2 * 64 * 256, wide = (size_t)3 * 3 * 64 * 256;
+  const size_t narrow = (size_t)wgrad4_stages() * 2 * 64 * 256, wide = (size_t)3 * 3 * 64 * 256;
   return wgrad4_tile_m(256, 1 << 20) == 256 ? std::max(narrow, wide) : narrow;
 }
 
 // shape part of the envelope (sedt_igemm_splitk sizes the split for the 128x128 tiling when this holds)
 bool wgrad4_shape_ok(int M, int N) {
-  static int mn = -1;
-  if (mn < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD4_MIN");
-    mn = e ? atoi(e) : 256;     // full-step sweep: 512 -> 6.32, 256 -> 6.27, 128 -> 6.30 ms
-  }
+  static const int mn = dev_int("SEDT_WGRAD4_MIN", 256);     // full-step sweep: 512 -> 6.32, 256 -> 6.27, 128 -> 6.30 ms
   return M >= mn && N >= mn && (M % 128) == 0 && (N % 128) == 0;
 }
 
 bool wgrad4_ok(const SedtIgemm& p) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD_V4");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
+  static const int on = dev_int("SEDT_WGRAD_V4", 1);
   // problems with a fused bias gradient are the transformer linears: measured on the full step they are better off in the
   // 64x64 grouped launch with the rest of their layer (6.05 vs 6.10-6.13 ms); SEDT_WGRAD4_BIAS=1 sends them here (tests do)
-  static int with_bias = -1;
-  if (with_bias < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD4_BIAS");
-    with_bias = (e && e[0] == '1') ? 1 : 0;
-  }
+  static const int with_bias = dev_int("SEDT_WGRAD4_BIAS", 0);
   return on && p.trans && wgrad4_shape_ok(p.M, p.N) && (p.colsum_out == nullptr || with_bias) && p.out_f32 &&
          (p.splitk > 1 ? p.slab != nullptr : ((p.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0)) &&
          (reinterpret_cast<uintptr_t>(p.slab) & 15) == 0;
@@ -410,50 +390,24 @@ bool wgrad4_ok(const SedtIgemm& p) {
 
 // channel-block-major tile order for the 3x3 problems (see wgrad4_impl); SEDT_WGRAD4_CBMAJOR=0/1 in the developer build
 static bool wg4_cbmajor(const SedtIgemm& p) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = sedt::dev_getenv("SEDT_WGRAD4_CBMAJOR");
-    // same-box A/B on the C2 step (profiles/r06_ab_wgrad4_cbmajor.txt): FETCH_SIZE of the wgrad4 launches 2.38 -> 2.08 GB (x2-corrected),
-    // their L2 hit rate 0.44 -> 0.50, step 5.142-5.173 -> 5.134-5.168 ms: a seventh less fabric traffic and no measurable time - the
-    // launches are not bound by it.  On by default because it is never slower
-    on = e ? atoi(e) : 1;
-  }
+  // same-box A/B on the C2 step (profiles/r06_ab_wgrad4_cbmajor.txt): FETCH_SIZE of the wgrad4 launches 2.38 -> 2.08 GB (x2-corrected),
+  // their L2 hit rate 0.44 -> 0.50, step 5.142-5.173 -> 5.134-5.168 ms: a seventh less fabric traffic and no measurable time - the
+  // launches are not bound by it.  On by default because it is never slower
+  static const int on = dev_int("SEDT_WGRAD4_CBMAJOR", 1);
   return on && p.conv && p.KH * p.KW > 1 && (p.Ci % 128) == 0 && p.N == p.KH * p.KW * p.Ci;
 }
 
-template <typename K>
-static int wg4_attr(K kern, const char* what) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg4_lds());
-  if (e != hipSuccess) {
-    set_error("%s: hipFuncSetAttribute failed: %s", what, hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
-
-int launch_wgrad4(const SedtIgemm& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
-  SEDT_DESCRIBE("wgrad4_kernel<%d>", wg4_stages());
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (wg4_attr(wgrad4_kernel<3>, "wgrad4") || wg4_attr(wgrad4_kernel<4>, "wgrad4")) return 1;
-    attr_set = true;
-  }
-  const int bm = wgrad4_tile_m(p.M, p.N);
-  const int nwg = (p.N / 128) * (p.M / bm);
-  const int nmajor = (p.N > p.M ? 1 : 0) | (bm == 256 ? 2 : 0);
+// a plan of LDS_WGRAD4: bm = wgrad4_tile_m, s = wgrad4_stages
+int launch_wgrad4(const LdsPlan& pl, const SedtIgemm& p, hipStream_t st) {
+  const int nwg = (p.N / 128) * (p.M / pl.bm);
+  const int nmajor = (p.N > p.M ? 1 : 0) | (pl.bm == 256 ? 2 : 0);
   const dim3 grid(nwg, p.splitk > 1 ? p.splitk : 1);
-  if (wg4_stages() == 4) hipLaunchKernelGGL(wgrad4_kernel<4>, grid, dim3(512), wg4_lds(), st, p, a_bytes, b_bytes, nmajor);
-  else hipLaunchKernelGGL(wgrad4_kernel<3>, grid, dim3(512), wg4_lds(), st, p, a_bytes, b_bytes, nmajor);
-  return check_launch("wgrad4");
+  if (pl.s == 4) return lds_launch_kernel<wgrad4_kernel<4>>("wgrad4", wg4_lds(), grid, 512, st, p, pl.a_bytes, pl.b_bytes, nmajor);
+  return lds_launch_kernel<wgrad4_kernel<3>>("wgrad4", wg4_lds(), grid, 512, st, p, pl.a_bytes, pl.b_bytes, nmajor);
 }
 
 // launches the (already validated, all wgrad4_ok) problems of g as one grouped kernel; nwg / blk0 are filled here
 int launch_wgrad4_group(WgradGroup& g, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (wg4_attr(wgrad4_group_kernel<3>, "wgrad4 group") || wg4_attr(wgrad4_group_kernel<4>, "wgrad4 group")) return 1;
-    attr_set = true;
-  }
   int blk = 0;
   for (int i = 0; i < g.n; ++i) {
     const SedtIgemm& p = g.p[i];
@@ -464,9 +418,8 @@ int launch_wgrad4_group(WgradGroup& g, hipStream_t st) {
     blk += (g.nwg[i] * (p.splitk > 1 ? p.splitk : 1) + 7) / 8 * 8;
   }
   g.blk0[g.n] = blk;
-  if (wg4_stages() == 4) hipLaunchKernelGGL(wgrad4_group_kernel<4>, dim3(blk), dim3(512), wg4_lds(), st, g);
-  else hipLaunchKernelGGL(wgrad4_group_kernel<3>, dim3(blk), dim3(512), wg4_lds(), st, g);
-  return check_launch("wgrad4_group");
+  if (wgrad4_stages() == 4) return lds_launch_kernel<wgrad4_group_kernel<4>>("wgrad4_group", wg4_lds(), dim3(blk), 512, st, g);
+  return lds_launch_kernel<wgrad4_group_kernel<3>>("wgrad4_group", wg4_lds(), dim3(blk), 512, st, g);
 }
 
 }  // namespace sedt

@@ -291,7 +291,7 @@ def _x3_rows(M, conv):
 
 
 def _x3_fast_ok(M, N, K, A, lda, B, ldb, Cout, ldc, kw):
-    """envelope of the LDS-DMA forward / dgrad kernels on the tripled contraction (igemm_lds_try, csrc/igemm3.hip) with f32 epilogue operands"""
+    """envelope of the LDS-DMA forward / dgrad kernels on the tripled contraction (lds_plan, csrc/igemm3.hip) with f32 epilogue operands"""
     conv = kw.get('conv')
     if not X3_FAST or kw.get('trans', 0) or kw.get('splitk', 1) > 1 or kw.get('act', ACT_NONE) == ACT_SIGMOID or kw.get('slab') is not None:
         return False
@@ -313,12 +313,23 @@ def _x3_fast_ok(M, N, K, A, lda, B, ldb, Cout, ldc, kw):
         return False
     if mask is not None and kw.get('mask_bits') and (mask.data_ptr() % 4 or kw.get('ldm', 0) % 4):     # 1-bit image: ldm in BYTES (igemm3.hip envelope)
         return False
-    for k_ in ('scale', 'bias'):                      # per-column epilogue operands are read as 16-byte vectors (igemm_lds_try)
+    for k_ in ('scale', 'bias'):                      # per-column epilogue operands are read as 16-byte vectors (lds_plan)
         t_ = kw.get(k_)
         if t_ is not None and t_.data_ptr() % 16:
             return False
     rows = _x3_rows(M, conv)
     return rows * 3 * Ci * 2 < (1 << 31) and N * 3 * K * 2 < (1 << 31)
+
+
+def _describe(a, code, njobs=0):
+    """the kernel instance sedt_igemm runs the problem `a` on, or (njobs > 0) sedt_igemm_group the njobs problems of the array `a`, as a
+    profiler prints it; None when the call is refused.  Nothing is launched"""
+    buf = C.create_string_buffer(160)
+    if njobs:
+        r = L.load().sedt_igemm_group_describe(a, njobs, code, buf, 160)
+    else:
+        r = L.load().sedt_igemm_describe(C.byref(a), code, 0, buf, 160)
+    return buf.value.decode() if r == 0 else None
 
 
 def _igemm_x3_fast(M, N, K, A, lda, B, ldb, Cout, ldc, kw):
@@ -346,9 +357,9 @@ def _igemm_x3_fast(M, N, K, A, lda, B, ldb, Cout, ldc, kw):
     if PROFILE is not None:
         PROFILE.append((a, BF16, (M, N, 3 * K, 0, 0 if conv is None else 1), (A, B, Cout, kw, A3, B3), PROFILE_HINT))
     if L.LAUNCH_LOG is not None:
-        buf = C.create_string_buffer(160)
-        if L.load().sedt_igemm_describe(C.byref(a), BF16, 0, buf, 160) == 0:
-            L.LAUNCH_LOG['igemm_x3:' + buf.value.decode()] += 1
+        name = _describe(a, BF16)
+        if name is not None:
+            L.LAUNCH_LOG['igemm_x3:' + name] += 1
     L.check(L.load().sedt_igemm(C.byref(a), BF16, L.stream_ptr()), 'sedt_igemm_x3')
 
 
@@ -365,8 +376,7 @@ def igemm(dtype, M, N, K, A, lda, B, ldb, Cout, ldc, **kw):
         # an f32 OUTPUT of bf16 operands (SP-SEDT's feature_align head: 12,000 x 2048 at C4): the LDS-DMA kernels write f32 through
         # their f32 epilogue (SedtIgemm.f32ep); asked for only when the dispatcher says the problem is inside their envelope
         a.f32ep = 1
-        buf = C.create_string_buffer(96)
-        if L.load().sedt_igemm_describe(C.byref(a), L.gemm_dtype(dtype), 0, buf, 96) != 0 or not buf.value.decode().startswith('igemm3'):
+        if not (_describe(a, L.gemm_dtype(dtype)) or '').startswith('igemm3'):
             a.f32ep = 0
     if _co['on'] and POOL.gemms and not trans and dtype == BF16:
         riders = POOL.take(((M + 63) // 64) * ((N + 63) // 64))
@@ -379,9 +389,9 @@ def igemm(dtype, M, N, K, A, lda, B, ldb, Cout, ldc, **kw):
     if PROFILE is not None:     # the operand tensors are kept alive so that the launch can be replayed for timing
         PROFILE.append((a, L.gemm_dtype(dtype), (M, N, K, trans, 0 if conv is None else 1), (A, B, Cout, kw), PROFILE_HINT))
     if L.LAUNCH_LOG is not None:     # (lib.launch_log(): also which kernel instance the dispatcher picks for this problem)
-        buf = C.create_string_buffer(160)
-        if L.load().sedt_igemm_describe(C.byref(a), L.gemm_dtype(dtype), 0, buf, 160) == 0:
-            L.LAUNCH_LOG['igemm:' + buf.value.decode().split('(')[0]] += 1
+        name = _describe(a, L.gemm_dtype(dtype))
+        if name is not None:
+            L.LAUNCH_LOG['igemm:' + name.split('(')[0]] += 1
     L.check(L.load().sedt_igemm(C.byref(a), L.gemm_dtype(dtype), L.stream_ptr()), 'sedt_igemm')
 
 
@@ -453,11 +463,7 @@ def skinny_linear_bwd(dtype, g, ysaved, w, x, act=ACT_NONE, mask=None, need_gx=T
 def _group_label(jobs):
     """bench.py's recorded step runs a group's problems one by one; this is the kernel instance the UN-recorded step launches them on as one
     group (sedt_igemm_group_describe), so that roofline.families books their flops on the row that actually ran"""
-    arr = (L.SedtIgemm * len(jobs))(*jobs)
-    buf = C.create_string_buffer(160)
-    if L.load().sedt_igemm_group_describe(arr, len(jobs), BF16, buf, 160) != 0:
-        return None
-    return buf.value.decode() or None
+    return _describe((L.SedtIgemm * len(jobs))(*jobs), BF16, len(jobs)) or None
 
 
 def linear_group(dtype, items):

@@ -60,7 +60,7 @@ def wg(name, Co, Ci, rows, expect, mode='bf16', a_off=0, a_pad=0, b_off=0, b_pad
 
 
 CASES = [
-    # ---- forward / dgrad LDS-DMA family (igemm_lds_try): tile rule, ring depth, the 16-wave forms
+    # ---- forward / dgrad LDS-DMA family (lds_plan, csrc/igemm3.hip): tile rule, ring depth, the 16-wave forms
     lin('k64_one_block', 200, 96, 64, I3_1),                                    # K == one K tile: the 1-stage ring
     lin('k256_m_tail1', 129, 192, 256, I3_2),                                   # M % 64 == 1, S = 2 below K = 320
     lin('k256_m_lt_tile', 40, 72, 256, I3_2),                                   # M and N smaller than one tile, N % 64 == 8

@@ -5,9 +5,13 @@
 * The split-K rule (sedt_igemm_splitk) gives a factor between 1 and the number of K blocks for every weight gradient of the training
   step and of the table, and the table keeps the split cases that matter: factor 1, 2, an odd one, a multiple of 8, a split whose
   trailing slice gets no K block (the kernels must write zero partial tiles for it) and the <= 2-tile long-K form (up to 512 slices).
+* The whole dispatch - status, instance and split factor of some 27 000 problems around every threshold (tests/gemm_dispatch_sweep.py) -
+  equals the record of tests/golden/g22_gemm_dispatch.npz (tests/golden/make_golden_dispatch.py).
 """
 import ctypes as C
+import os
 
+import numpy as np
 import pytest
 
 import gemm_cases as G
@@ -118,3 +122,20 @@ def test_table_keeps_the_split_edge_cases(lib):
     assert empty_lds, 'no LDS-DMA wgrad case leaves an empty trailing split-K slice'
     assert long_k, 'no <= 2-tile long-K case'
     assert any(c['name'] in empty_lds for c in G.GROUP_WGRAD), 'the grouped wgrad launch has no empty-slice problem'
+
+
+def test_dispatch_sweep_equals_the_record(lib):
+    import gemm_dispatch_sweep as S
+    rec = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g22_gemm_dispatch.npz'))
+    want = [str(a) for a in rec['answers'][rec['index']]]
+    got = S.answers(lib)
+    # the sweep itself: large enough, almost all of it problems the library accepts, every instance of the envelope table in it
+    assert len(got) >= 20000 and len(got) == len(want), (len(got), len(want))
+    parts = [a.split('|')[:2] for a in want]
+    refused = sum(any(not q.startswith('0:') for q in ps) for ps in parts)
+    assert refused <= 0.02 * len(want), (refused, len(want))
+    seen = {q.split(':', 1)[1] for ps in parts for q in ps}
+    assert S.table_instances() <= seen, sorted(S.table_instances() - seen)
+    # every status, label and split factor
+    diff = [(i, w, g) for i, (w, g) in enumerate(zip(want, got)) if w != g]
+    assert not diff, '%d of %d problems moved, the first: %s' % (len(diff), len(want), diff[:5])
