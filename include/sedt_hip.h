@@ -31,6 +31,8 @@
  *                                                                             utilities/BoxEncoder.py:179-226, engine.py:199-297,
  *                                                                             utilities/metrics.py:43-80, 281-322
  *   sedt_event_segment_metrics_update                                         + sed_eval segment-based counts  utilities/metrics.py:83-116
+ *   sedt_decode_events                                                        decode_strong + the clip, written out as event records
+ *                                                                             utilities/BoxEncoder.py:179-226, engine.py:218-297
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -799,6 +801,21 @@ int sedt_event_segment_metrics_update(const float* scores, const int64_t* labels
                                       double max_len, double t_collar, double pct, int del_overlap, int optimal, int64_t* ev_counts,
                                       int64_t* tag_counts, double time_resolution, int n_seg_words, int64_t* seg_counts,
                                       int64_t* sdi_counts, void* stream);
+
+/* sedt_decode_events (engine.py:218-297 with utilities/BoxEncoder.py:179-226): the predictions themselves.  One wave per (clip,
+ * threshold) of one fusion strategy's PostProcess outputs (scores [B][Q] f32, labels [B][Q] int64, boxes [B][Q][2] f32 seconds);
+ * thresholds [K] f32 is a DEVICE vector read by every launch (a captured graph follows an edited grid), 1 <= K <= 1024.
+ * Decode, all in f32: a query is kept when score >= threshold (del_overlap) or score > threshold (!del_overlap), offset - onset >=
+ * min_duration and 0 <= label < C.  With del_overlap the classes come in the order of their first kept query (the reference's dict
+ * insertion order, fixed before any deletion), the events of a class by onset (ties: lower query first), swept once: an event
+ * starting before the end of the last one still standing replaces it when its score is strictly higher, else is dropped.  Without
+ * del_overlap: the kept queries in query order.  Onsets / offsets are then clipped to [0, max_len]; max_len must be a value float32
+ * represents exactly (refused otherwise), +inf = no clip at all.  An event clipped to zero length stays.
+ * out [K][B][1 + 5 Q] 32-bit words: word 0 = the event count n, then Q slots {class int32, onset f32, offset f32, score f32, query
+ * int32} in output order; every slot at or past n is written as {-1, 0, 0, 0, -1} by every launch.  Plain stores, no atomics.
+ * Q <= 64, C <= 63. */
+int sedt_decode_events(const float* scores, const int64_t* labels, const float* boxes, const float* thresholds, int B, int Q, int C,
+                       int K, float min_duration, double max_len, int del_overlap, int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------ input side on the device (utilities/BoxTransforms.py,
  * utilities/mixup.py)

@@ -722,13 +722,16 @@ def _tensors(x):
 
 # ---------------------------------------------------------------------------------------------------- validation / prediction
 def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_strategy=(1,), at=True, threshold=0.5, metrics=None,
-                 clip_idx=None):
+                 clip_idx=None, decoder=None):
     """The per-batch body of reference engine.get_sedt_predictions (engine.py:244-285) on the device: no-grad forward, the
     losses the reference logs (criterion with strong_mask = the whole batch), the thresholded audio tags, and
     ``postprocessors['bbox']`` once per fusion strategy.  Returns (loss_dict, audio_tags or None, {at_m: (scores [B,Q], labels
     [B,Q], boxes [B,Q,2] in seconds)}).  With ``metrics`` (utilities.metrics.EventMetrics) the decode and the event-based /
     clip-level counts of the batch (clips ``clip_idx`` of the metrics' reference) are added on the device as well; without it
-    the decoding into event lists stays the caller's, as in the reference."""
+    the counters are left alone.  With ``decoder`` (utilities.predictions.EventDecoder) the batch is also decoded into event records
+    on the device (decode_strong at every threshold of the decoder's grid, clipped to the clip length) and their copy to the host
+    is enqueued: a fourth value is returned, the handle whose ``rows()`` waits for the copy and unpacks.  Without either, the
+    decoding into event lists stays the caller's, as in the reference."""
     with torch.no_grad():
         outputs = model(batch_input)
         B = outputs['pred_logits'].shape[0]
@@ -743,12 +746,21 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
             if clip_idx is None:
                 raise ValueError('predict_step(metrics=...) needs the clip indices of the batch (clip_idx)')
             metrics.update(results, audio_tags, clip_idx)
+        if decoder is not None:
+            _check_decoder(decoder, fusion_strategy)
+            decoder.decode(results, audio_tags)
+            return loss_dict, audio_tags, results, decoder.fetch()
     return loss_dict, audio_tags, results
 
 
 def _check_metrics(metrics, fusion_strategy):
     if tuple(fusion_strategy) != metrics.fusion:
         raise ValueError(f'EventMetrics counts fusion strategies {metrics.fusion}, the predict step runs {tuple(fusion_strategy)}')
+
+
+def _check_decoder(decoder, fusion_strategy):
+    if tuple(fusion_strategy) != decoder.fusion:
+        raise ValueError(f'EventDecoder decodes fusion strategies {decoder.fusion}, the predict step runs {tuple(fusion_strategy)}')
 
 
 class GraphedPredictStep(object):
@@ -759,10 +771,15 @@ class GraphedPredictStep(object):
 
     ``metrics`` (utilities.metrics.EventMetrics, its reference set before the step is built): the graph also decodes every clip
     and adds the event-based / clip-level counts to the metrics' device counters; each call then takes the batch's clip indices,
-    and a validation epoch is N replays and one ``metrics.compute()``.  Building the step leaves the counters as they were."""
+    and a validation epoch is N replays and one ``metrics.compute()``.  Building the step leaves the counters as they were.
+
+    ``decoder`` (utilities.predictions.EventDecoder): the graph also decodes every clip into event records at every threshold of
+    the decoder's grid (a device vector: ``decoder.set_thresholds`` is followed by the next replay); each call enqueues the copy of
+    the records to the host after the replay and returns the handle as a fourth value.  ``metrics`` and ``decoder`` may be given
+    together."""
 
     def __init__(self, model, criterion, postprocessor, example_input, example_targets, fusion_strategy=(1,), at=True, threshold=0.5,
-                 max_targets=32, warmup=2, metrics=None):
+                 max_targets=32, warmup=2, metrics=None, decoder=None):
         from .sedt import TargetTables
         self.model, self.criterion, self.post = model, criterion, postprocessor
         self.fusion, self.at, self.threshold = tuple(fusion_strategy), at, threshold
@@ -771,7 +788,9 @@ class GraphedPredictStep(object):
         B = len(example_targets)
         self.tables = TargetTables(B, B, B, dev, max_targets=max_targets, with_ratio=False, weak_mask_none=True).load(example_targets)
         self.sizes = torch.stack([t['orig_size'] for t in example_targets], dim=0).to(dev).float().clone()
-        self.metrics = metrics
+        self.metrics, self.decoder = metrics, decoder
+        if decoder is not None:
+            _check_decoder(decoder, self.fusion)
         if metrics is not None:
             _check_metrics(metrics, self.fusion)
             if metrics.table is None:
@@ -798,6 +817,8 @@ class GraphedPredictStep(object):
             res = {m: self.post.batched(outputs, self.sizes, audio_tags=tags, at_m=m, threshold=self.threshold) for m in self.fusion}
             if self.metrics is not None:
                 self.metrics.update(res, tags, self.clip_idx)
+            if self.decoder is not None:
+                self.decoded = self.decoder.decode(res, tags)           # the static buffers the captured launches fill
         return losses, tags, res
 
     def __call__(self, batch_input, targets, clip_idx=None):
@@ -813,6 +834,8 @@ class GraphedPredictStep(object):
                 clip_idx = self.metrics.host_clip_index(clip_idx)
             self.clip_idx.copy_(clip_idx, non_blocking=True)
         self.graph.replay()
+        if self.decoder is not None:
+            return self.out + (self.decoder.fetch(self.decoded),)
         return self.out
 
 
@@ -834,6 +857,44 @@ def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, 
             predict_step(model, criterion, postprocessor, x, targets, fusion_strategy=metrics.fusion, at=at, threshold=threshold,
                          metrics=metrics, clip_idx=idx)
     return metrics.compute()
+
+
+def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, filenames, at=True, graphed=True, metrics=None,
+                         max_targets=32, threshold=0.5, step=None):
+    """engine.get_sedt_predictions (engine.py:218-297) with the decode on the device: ``batches`` yields (input, targets, clip
+    indices) as for evaluate_events, ``decoder`` is a utilities.predictions.EventDecoder and ``filenames`` the dataset's clip names
+    (indexed by clip index).  Returns (audio-tag table, {at_m: PredictionSet}): the reference's audio_tag_dfs and dec_prediction_dfs,
+    the latter at every threshold of the decoder's grid.  Every batch goes through one GraphedPredictStep(decoder=...) replay (a batch
+    of another size through the eager predict_step with the same kernels); the records of batch i - 1 are unpacked on the host after
+    batch i is enqueued, so the host formatting overlaps the device.  With ``metrics`` (EventMetrics, its reference set) the same pass
+    resets and fills the counters: ``metrics.compute()`` afterwards gives evaluate_events' scores.  ``step``: a
+    GraphedPredictStep built with this decoder (and these metrics) to replay instead of capturing a new one, for a validation pass
+    per epoch."""
+    from .utilities import predictions as P
+    fusion = decoder.fusion
+    if metrics is not None:
+        _check_metrics(metrics, fusion)
+        metrics.reset()
+    tag_table, sets = P.TagTable(), decoder.prediction_sets()
+    if step is not None and (step.decoder is not decoder or step.metrics is not metrics or step.fusion != fusion):
+        raise ValueError('get_sedt_predictions: the step was built with another decoder, metrics or fusion strategy')
+    pending = None
+    for x, targets, idx in batches:
+        if graphed and step is None:
+            step = GraphedPredictStep(model, criterion, postprocessor, x, targets, fusion_strategy=fusion, at=at, threshold=threshold,
+                                      max_targets=max_targets, metrics=metrics, decoder=decoder)
+        if step is not None and x.shape == step.static_x.shape:
+            fetched = step(x, targets, idx if metrics is not None else None)[3]
+        else:
+            fetched = predict_step(model, criterion, postprocessor, x, targets, fusion_strategy=fusion, at=at, threshold=threshold,
+                                   metrics=metrics, clip_idx=idx if metrics is not None else None, decoder=decoder)[3]
+        names = [filenames[int(k)] for k in idx]
+        if pending is not None:
+            P.collect(*pending, tag_table, sets, decoder.labels)
+        pending = (fetched, names)
+    if pending is not None:
+        P.collect(*pending, tag_table, sets, decoder.labels)
+    return tag_table, sets
 
 
 def pseudo_label_tables(tea_outputs, classwise_threshold, orig_size, tables, counter=None, del_overlap=True):

@@ -1882,6 +1882,38 @@ def event_metrics_update(scores, labels, boxes, at_tags, clip_idx, table, n_clip
         float(time_resolution), int(n_seg_words), _p(seg_counts), _p(sdi_counts), L.stream_ptr()), 'event_segment_metrics_update')
 
 
+DECODE_MAX_THRESHOLDS = 1024      # csrc/decode.hip: SEDT_DE_MAXK
+
+
+def decode_events_views(packed, Q):
+    """typed views on a packed decode buffer [K, B, 1 + 5 Q] (int32; a device tensor, a host tensor or a numpy array alike):
+    (count [K,B] int32, class [K,B,Q] int32, times [K,B,Q,2] f32 {onset, offset}, score [K,B,Q] f32, query [K,B,Q] int32)"""
+    f32 = torch.float32 if torch.is_tensor(packed) else np.float32
+    K, B = packed.shape[0], packed.shape[1]
+    slots = packed[:, :, 1:].reshape(K, B, Q, 5)
+    return packed[:, :, 0], slots[..., 0], slots[..., 1:3].view(f32), slots[..., 3].view(f32), slots[..., 4]
+
+
+def decode_events(scores, labels, boxes, thresholds, n_classes, min_duration=0.2, max_len=10.0, del_overlap=True, out=None):
+    """decode_strong + the clip to [0, max_len] of one fusion strategy's PostProcess outputs (scores [B,Q] f32, labels [B,Q] int64,
+    boxes [B,Q,2] f32 seconds) at every threshold of the DEVICE f32 vector ``thresholds`` [K], written out as event records in the
+    reference's output order (include/sedt_hip.h: sedt_decode_events).  max_len: a value float32 holds exactly, inf = no clip.
+    Returns (packed, count, class, times, score, query): the int32 buffer [K, B, 1 + 5 Q] (``out`` when given) and
+    decode_events_views of it."""
+    _dev_check(scores, labels, boxes, thresholds, out)
+    B, Q = scores.shape
+    K = thresholds.numel()
+    assert scores.dtype == torch.float32 and labels.dtype == torch.int64 and boxes.dtype == torch.float32
+    assert scores.is_contiguous() and labels.is_contiguous() and boxes.is_contiguous() and tuple(boxes.shape) == (B, Q, 2)
+    assert tuple(labels.shape) == (B, Q) and thresholds.dtype == torch.float32 and thresholds.dim() == 1 and thresholds.is_contiguous()
+    if out is None:
+        out = torch.empty((K, B, 1 + 5 * Q), device=scores.device, dtype=torch.int32)
+    assert out.dtype == torch.int32 and tuple(out.shape) == (K, B, 1 + 5 * Q) and out.is_contiguous()
+    L.check(L.load().sedt_decode_events(_p(scores), _p(labels), _p(boxes), _p(thresholds), B, Q, int(n_classes), K, float(min_duration),
+                                        float(max_len), int(bool(del_overlap)), _p(out), L.stream_ptr()), 'decode_events')
+    return (out,) + decode_events_views(out, Q)
+
+
 def mixup(x1, x2, jobs, out=None):
     """feature half of utilities/mixup.py: out[i] = lam * x1[src1] + (1 - lam) * x2[src2] / x1[src1] / x2[src2] per job record
     (jobs: uint8 device tensor of n 16-byte records {int32 src1, src2, mode; f32 lam}); x1 / x2 / out f32 [*, clip...]"""
