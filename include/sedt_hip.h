@@ -33,6 +33,8 @@
  *   sedt_event_segment_metrics_update                                         + sed_eval segment-based counts  utilities/metrics.py:83-116
  *   sedt_decode_events                                                        decode_strong + the clip, written out as event records
  *                                                                             utilities/BoxEncoder.py:179-226, engine.py:218-297
+ *   sedt_psds_update                                                          PSDS confusion counts from those event records
+ *                                                                             utilities/metrics.py:120-145, 325-330 (psds_eval)
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -816,6 +818,29 @@ int sedt_event_segment_metrics_update(const float* scores, const int64_t* labels
  * Q <= 64, C <= 63. */
 int sedt_decode_events(const float* scores, const int64_t* labels, const float* boxes, const float* thresholds, int B, int Q, int C,
                        int K, float min_duration, double max_len, int del_overlap, int32_t* out, void* stream);
+
+/* sedt_psds_update (utilities/metrics.py:120-145, 325-330: psds_eval's PSDSEval restated, utilities/psds.py holds the definition): the
+ * per-operating-point confusion counts of the polyphonic sound detection score, from the buffer sedt_decode_events just wrote.  One
+ * wave per (clip, threshold); the decode is not repeated.
+ * records [K][B][1 + 5 Q]: sedt_decode_events' `out`.  A record whose count is outside 0 .. Q is skipped whole; a live slot whose class
+ * is outside 0 .. C - 1 or whose offset - onset is not > 0 is skipped; neither is ever used as an index.
+ * Reference table: sedt_event_metrics_update's (ref_present, ref_off, ref_cls, ref_on, ref_end, n_clips, max_ref <= 64, clip_idx with
+ * the same rule: -1, an index >= n_clips or ref_present 0 = a clip outside the table, which adds nothing), plus ref_dur [n_clips]
+ * float64: the clip's duration D_k in seconds.  A reference event whose class is outside 0 .. C - 1 or whose duration is not > 0 takes
+ * part in nothing.  A clip in the table with no events is scored (its detections can only be false positives).
+ * Per clip and threshold, float64 on the records' f32 values widened; inter(d, g) = min(off_d, off_g) - max(on_d, on_g) counts only
+ * where > 0; every term is a plain division added to a running sum (no contraction), references in table order, detections in record
+ * order; comparisons are >=:
+ *   DTC   p_d = sum over the references g of d's class of inter(d, g) / dur_d;  d passes when p_d >= dtc;
+ *   GTC   v_g = sum over the detections d of g's class that passed of inter(d, g) / dur_g;  v_g >= gtc: counts[c][c] += 1;
+ *   CTTC  for every d that failed and every other class c': sum over the references g of c' of inter(d, g) / dur_d >= cttc:
+ *         counts[class(d)][c'] += 1;  and (min(off_d, D_k) - max(on_d, 0)) / dur_d >= cttc: counts[class(d)][C] += 1 (false positive).
+ * counts [n_fusion][K][C][C + 1] int64, row `fusion` accumulated with integer atomics only (zero them per validation set).
+ * 1 <= Q <= 64, 1 <= C <= 63, 1 <= K <= 1024, max_ref <= 64, B >= 0 (B == 0 launches nothing); dtc, gtc, cttc not NaN. */
+int sedt_psds_update(const int32_t* records, const int32_t* clip_idx, const int32_t* ref_present, const int32_t* ref_off,
+                     const int32_t* ref_cls, const double* ref_on, const double* ref_end, const double* ref_dur, int n_clips,
+                     int max_ref, int B, int Q, int C, int K, int n_fusion, int fusion, double dtc, double gtc, double cttc,
+                     int64_t* counts, void* stream);
 
 /* ------------------------------------------------------------------ input side on the device (utilities/BoxTransforms.py,
  * utilities/mixup.py)

@@ -722,7 +722,7 @@ def _tensors(x):
 
 # ---------------------------------------------------------------------------------------------------- validation / prediction
 def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_strategy=(1,), at=True, threshold=0.5, metrics=None,
-                 clip_idx=None, decoder=None):
+                 clip_idx=None, decoder=None, psds=None):
     """The per-batch body of reference engine.get_sedt_predictions (engine.py:244-285) on the device: no-grad forward, the
     losses the reference logs (criterion with strong_mask = the whole batch), the thresholded audio tags, and
     ``postprocessors['bbox']`` once per fusion strategy.  Returns (loss_dict, audio_tags or None, {at_m: (scores [B,Q], labels
@@ -731,7 +731,13 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
     the counters are left alone.  With ``decoder`` (utilities.predictions.EventDecoder) the batch is also decoded into event records
     on the device (decode_strong at every threshold of the decoder's grid, clipped to the clip length) and their copy to the host
     is enqueued: a fourth value is returned, the handle whose ``rows()`` waits for the copy and unpacks.  Without either, the
-    decoding into event lists stays the caller's, as in the reference."""
+    decoding into event lists stays the caller's, as in the reference.  With ``psds`` (utilities.psds.PsdsMetrics, bound to this
+    ``decoder``) the PSDS confusion counts of the batch's records (clips ``clip_idx`` of its reference) are added on the device by the
+    launch after the decode's."""
+    if psds is not None:
+        _check_psds(psds, decoder)
+        if clip_idx is None:
+            raise ValueError('predict_step(psds=...) needs the clip indices of the batch (clip_idx)')
     with torch.no_grad():
         outputs = model(batch_input)
         B = outputs['pred_logits'].shape[0]
@@ -748,7 +754,9 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
             metrics.update(results, audio_tags, clip_idx)
         if decoder is not None:
             _check_decoder(decoder, fusion_strategy)
-            decoder.decode(results, audio_tags)
+            decoded = decoder.decode(results, audio_tags)
+            if psds is not None:
+                psds.update(decoded, clip_idx)
             return loss_dict, audio_tags, results, decoder.fetch()
     return loss_dict, audio_tags, results
 
@@ -761,6 +769,11 @@ def _check_metrics(metrics, fusion_strategy):
 def _check_decoder(decoder, fusion_strategy):
     if tuple(fusion_strategy) != decoder.fusion:
         raise ValueError(f'EventDecoder decodes fusion strategies {decoder.fusion}, the predict step runs {tuple(fusion_strategy)}')
+
+
+def _check_psds(psds, decoder):
+    if decoder is None or psds.decoder is not decoder:
+        raise ValueError('psds= scores the event records of the EventDecoder it was built with: pass that decoder as decoder=')
 
 
 class GraphedPredictStep(object):
@@ -776,10 +789,14 @@ class GraphedPredictStep(object):
     ``decoder`` (utilities.predictions.EventDecoder): the graph also decodes every clip into event records at every threshold of
     the decoder's grid (a device vector: ``decoder.set_thresholds`` is followed by the next replay); each call enqueues the copy of
     the records to the host after the replay and returns the handle as a fourth value.  ``metrics`` and ``decoder`` may be given
-    together."""
+    together.
+
+    ``psds`` (utilities.psds.PsdsMetrics, bound to ``decoder``, its reference set before the step is built): the launch after the
+    decode's adds the PSDS confusion counts of the records to the psds' device counters; each call takes the batch's clip indices.
+    Building the step leaves the counters as they were."""
 
     def __init__(self, model, criterion, postprocessor, example_input, example_targets, fusion_strategy=(1,), at=True, threshold=0.5,
-                 max_targets=32, warmup=2, metrics=None, decoder=None):
+                 max_targets=32, warmup=2, metrics=None, decoder=None, psds=None):
         from .sedt import TargetTables
         self.model, self.criterion, self.post = model, criterion, postprocessor
         self.fusion, self.at, self.threshold = tuple(fusion_strategy), at, threshold
@@ -788,19 +805,25 @@ class GraphedPredictStep(object):
         B = len(example_targets)
         self.tables = TargetTables(B, B, B, dev, max_targets=max_targets, with_ratio=False, weak_mask_none=True).load(example_targets)
         self.sizes = torch.stack([t['orig_size'] for t in example_targets], dim=0).to(dev).float().clone()
-        self.metrics, self.decoder = metrics, decoder
+        self.metrics, self.decoder, self.psds = metrics, decoder, psds
         if decoder is not None:
             _check_decoder(decoder, self.fusion)
-        if metrics is not None:
-            _check_metrics(metrics, self.fusion)
-            if metrics.table is None:
-                raise RuntimeError('GraphedPredictStep(metrics=...): call metrics.set_reference() before building the step')
+        if psds is not None:
+            _check_psds(psds, decoder)
+        self.counted = [m for m in (metrics, psds) if m is not None]   # what counts per clip: each takes the batch's clip indices
+        for m in self.counted:
+            if m is metrics:
+                _check_metrics(metrics, self.fusion)
+            if m.table is None:
+                raise RuntimeError('GraphedPredictStep(metrics= / psds=...): call set_reference() on it before building the step')
+        if self.counted:
             self.clip_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
-            self.metrics_gen = metrics.generation
-            saved = [t.clone() for t in metrics.counters()]            # the warm-up runs count too: put the counters back after
+            self.counted_gen = [m.generation for m in self.counted]
+            counters = [t for m in self.counted for t in m.counters()]
+            saved = [t.clone() for t in counters]                      # the warm-up runs count too: put the counters back after
         _warm_on_train_stream(dev, self._body, warmup)
-        if metrics is not None:
-            for t, s in zip(metrics.counters(), saved):
+        if self.counted:
+            for t, s in zip(counters, saved):
                 t.copy_(s)
             torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -819,19 +842,21 @@ class GraphedPredictStep(object):
                 self.metrics.update(res, tags, self.clip_idx)
             if self.decoder is not None:
                 self.decoded = self.decoder.decode(res, tags)           # the static buffers the captured launches fill
+                if self.psds is not None:
+                    self.psds.update(self.decoded, self.clip_idx)
         return losses, tags, res
 
     def __call__(self, batch_input, targets, clip_idx=None):
         self.static_x.copy_(batch_input, non_blocking=True)
         self.tables.load(targets)
         self.sizes.copy_(torch.stack([t['orig_size'] for t in targets], dim=0), non_blocking=True)
-        if self.metrics is not None:
+        if self.counted:
             if clip_idx is None:
-                raise ValueError('GraphedPredictStep(metrics=...) needs the clip indices of the batch (clip_idx)')
-            if self.metrics.generation != self.metrics_gen:
+                raise ValueError('GraphedPredictStep(metrics= / psds=...) needs the clip indices of the batch (clip_idx)')
+            if [m.generation for m in self.counted] != self.counted_gen:
                 raise RuntimeError('GraphedPredictStep: the metrics\' reference changed shape after the step was built; build a new step')
             if not (torch.is_tensor(clip_idx) and clip_idx.is_cuda):
-                clip_idx = self.metrics.host_clip_index(clip_idx)
+                clip_idx = [m.host_clip_index(clip_idx) for m in self.counted][0]       # checked against every table
             self.clip_idx.copy_(clip_idx, non_blocking=True)
         self.graph.replay()
         if self.decoder is not None:
@@ -860,7 +885,7 @@ def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, 
 
 
 def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, filenames, at=True, graphed=True, metrics=None,
-                         max_targets=32, threshold=0.5, step=None):
+                         max_targets=32, threshold=0.5, step=None, psds=None):
     """engine.get_sedt_predictions (engine.py:218-297) with the decode on the device: ``batches`` yields (input, targets, clip
     indices) as for evaluate_events, ``decoder`` is a utilities.predictions.EventDecoder and ``filenames`` the dataset's clip names
     (indexed by clip index).  Returns (audio-tag table, {at_m: PredictionSet}): the reference's audio_tag_dfs and dec_prediction_dfs,
@@ -868,26 +893,31 @@ def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, file
     of another size through the eager predict_step with the same kernels); the records of batch i - 1 are unpacked on the host after
     batch i is enqueued, so the host formatting overlaps the device.  With ``metrics`` (EventMetrics, its reference set) the same pass
     resets and fills the counters: ``metrics.compute()`` afterwards gives evaluate_events' scores.  ``step``: a
-    GraphedPredictStep built with this decoder (and these metrics) to replay instead of capturing a new one, for a validation pass
-    per epoch."""
+    GraphedPredictStep built with this decoder (and these metrics and psds) to replay instead of capturing a new one, for a validation
+    pass per epoch.  With ``psds`` (utilities.psds.PsdsMetrics bound to ``decoder``, its reference set) the same pass resets and fills
+    its counters: ``psds.compute()`` afterwards gives the PSD scores of the decoder's grid of operating points."""
     from .utilities import predictions as P
     fusion = decoder.fusion
     if metrics is not None:
         _check_metrics(metrics, fusion)
         metrics.reset()
+    if psds is not None:
+        _check_psds(psds, decoder)
+        psds.reset()
+    counted = metrics is not None or psds is not None
     tag_table, sets = P.TagTable(), decoder.prediction_sets()
-    if step is not None and (step.decoder is not decoder or step.metrics is not metrics or step.fusion != fusion):
-        raise ValueError('get_sedt_predictions: the step was built with another decoder, metrics or fusion strategy')
+    if step is not None and (step.decoder is not decoder or step.metrics is not metrics or step.psds is not psds or step.fusion != fusion):
+        raise ValueError('get_sedt_predictions: the step was built with another decoder, metrics, psds or fusion strategy')
     pending = None
     for x, targets, idx in batches:
         if graphed and step is None:
             step = GraphedPredictStep(model, criterion, postprocessor, x, targets, fusion_strategy=fusion, at=at, threshold=threshold,
-                                      max_targets=max_targets, metrics=metrics, decoder=decoder)
+                                      max_targets=max_targets, metrics=metrics, decoder=decoder, psds=psds)
         if step is not None and x.shape == step.static_x.shape:
-            fetched = step(x, targets, idx if metrics is not None else None)[3]
+            fetched = step(x, targets, idx if counted else None)[3]
         else:
             fetched = predict_step(model, criterion, postprocessor, x, targets, fusion_strategy=fusion, at=at, threshold=threshold,
-                                   metrics=metrics, clip_idx=idx if metrics is not None else None, decoder=decoder)[3]
+                                   metrics=metrics, clip_idx=idx if counted else None, decoder=decoder, psds=psds)[3]
         names = [filenames[int(k)] for k in idx]
         if pending is not None:
             P.collect(*pending, tag_table, sets, decoder.labels)

@@ -1914,6 +1914,28 @@ def decode_events(scores, labels, boxes, thresholds, n_classes, min_duration=0.2
     return (out,) + decode_events_views(out, Q)
 
 
+def psds_update(records, clip_idx, table, n_clips, max_ref, n_classes, counts, fusion, dtc=0.5, gtc=0.5, cttc=0.3):
+    """the PSDS confusion counts of one fusion strategy's event records (``records``: the int32 buffer [K, B, 1 + 5 Q] decode_events
+    filled), accumulated into counts int64 [n_fusion, K, C, C + 1] at row ``fusion`` (include/sedt_hip.h: sedt_psds_update).
+    table: event_metrics_update's device reference table plus 'dur' float64 [n_clips], the clips' durations in seconds;
+    clip_idx int32 [B] (-1 = outside the table).  Nothing is decoded again and nothing is read back."""
+    _dev_check(records, clip_idx, counts)
+    K, B = records.shape[0], records.shape[1]
+    C = int(n_classes)
+    Q = (records.shape[2] - 1) // 5
+    assert records.dtype == torch.int32 and records.dim() == 3 and records.shape[2] == 1 + 5 * Q and records.is_contiguous()
+    assert clip_idx.dtype == torch.int32 and clip_idx.numel() == B and clip_idx.is_contiguous()
+    nf = counts.shape[0]
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (nf, K, C, C + 1) and counts.is_contiguous()
+    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_clips + 1
+    assert table['present'].dtype == torch.int32 and table['present'].numel() >= n_clips
+    assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
+    assert table['dur'].dtype == torch.float64 and table['dur'].numel() >= n_clips
+    L.check(L.load().sedt_psds_update(_p(records), _p(clip_idx), _p(table['present']), _p(table['off']), _p(table['cls']), _p(table['on']),
+                                      _p(table['end']), _p(table['dur']), int(n_clips), int(max_ref), B, Q, C, K, nf, int(fusion),
+                                      float(dtc), float(gtc), float(cttc), _p(counts), L.stream_ptr()), 'psds_update')
+
+
 def mixup(x1, x2, jobs, out=None):
     """feature half of utilities/mixup.py: out[i] = lam * x1[src1] + (1 - lam) * x2[src2] / x1[src1] / x2[src2] per job record
     (jobs: uint8 device tensor of n 16-byte records {int32 src1, src2, mode; f32 lam}); x1 / x2 / out f32 [*, clip...]"""
