@@ -55,6 +55,11 @@ __global__ __launch_bounds__(1024) void set_criterion_kernel(const SedtCriterion
     nb = block_sum_1024(sv, red);
   }
   const float inv_nb = 1.f / nb;
+  // num_boxes = 0 with strong clips in the batch (none of them carries an event): the reference divides 0 by 0 in the box losses and its
+  // autograd forms inf - inf at the target column of the class gradient.  z is +0 for every finite 1 / num_boxes and NaN otherwise; adding
+  // it to those entries changes no bit of a finite result and gives the reference's NaN where it has one.  A batch WITHOUT any strong
+  // clip (split[0] = 0) has no such term at all: every row is skipped, the set losses are 0 and the total is the audio-tag loss
+  const float z = ns_eff > 0 ? 0.f * inv_nb : 0.f;
   // output slots: [4*d + 0..3] = ce, bbox, giou, cardinality of dense layer d; then class_error hits, matched count, weak
   const int SLOT_HIT = 4 * L, SLOT_CNT = 4 * L + 1, SLOT_WEAK = 4 * L + 2;
   for (int i = t; i < L * B; i += 1024) card[i] = 0;
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(1024) void set_criterion_kernel(const SedtCriterion
       const float gscale = coef * w * inv_nb;
 #pragma unroll
       for (int c = 0; c < XR; ++c)
-        if (c < C1) gx[c] = gscale * (__expf(xr[c] - lse) - (c == tc ? 1.f : 0.f));
+        if (c < C1) gx[c] = gscale * (__expf(xr[c] - lse) - (c == tc ? 1.f : 0.f)) + (c == tc ? z : 0.f);
     } else {
       float se = 0.f;
       for (int c = 0; c < C1; ++c) se += __expf(x[c] - m);
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(1024) void set_criterion_kernel(const SedtCriterion
       const float w = a.empty_weight[tc];
       l_ce = w * (lse - x[tc]) * coef * inv_nb;
       const float gscale = coef * w * inv_nb;
-      for (int c = 0; c < C1; ++c) gx[c] = gscale * (__expf(x[c] - lse) - (c == tc ? 1.f : 0.f));
+      for (int c = 0; c < C1; ++c) gx[c] = gscale * (__expf(x[c] - lse) - (c == tc ? 1.f : 0.f)) + (c == tc ? z : 0.f);
     }
     if (d == 0 && wb > 0.f) {
       n_cnt = 1.f;
@@ -167,14 +172,17 @@ __global__ __launch_bounds__(1024) void set_criterion_kernel(const SedtCriterion
       gc = gs + ge;
       gl = 0.5f * (ge - gs);
       // GIoU
+      // sub-gradients at coincident edges as the reference's autograd takes them: min / max split a tie evenly, clamp(min=0) passes
+      // at 0 (so an interval that only touches its target still feels the overlap term), |x| has slope 0 at 0
       const float lo = fmaxf(s1, s2), hi = fminf(e1, e2);
       const float inter = fmaxf(hi - lo, 0.f);
-      const float di_e = (hi - lo > 0.f && e1 < e2) ? 1.f : 0.f;     // d inter / d e1
-      const float di_s = (hi - lo > 0.f && s1 > s2) ? -1.f : 0.f;    // d inter / d s1
+      const float pass = hi - lo >= 0.f ? 1.f : 0.f;
+      const float di_e = pass * (e1 < e2 ? 1.f : e1 == e2 ? 0.5f : 0.f);      // d inter / d e1
+      const float di_s = pass * (s1 > s2 ? -1.f : s1 == s2 ? -0.5f : 0.f);    // d inter / d s1
       const float uni = (e1 - s1) + (e2 - s2) - inter;
       const float du_e = 1.f - di_e, du_s = -1.f - di_s;
       const float hull = fmaxf(fmaxf(e1, e2) - fminf(s1, s2), 0.f);
-      const float dh_e = e1 > e2 ? 1.f : 0.f, dh_s = s1 < s2 ? -1.f : 0.f;
+      const float dh_e = e1 > e2 ? 1.f : e1 == e2 ? 0.5f : 0.f, dh_s = s1 < s2 ? -1.f : s1 == s2 ? -0.5f : 0.f;
       const float giou = inter / uni - (hull - uni) / hull;
       l_gi = (1.f - giou) * wb * inv_nb;
       // d giou = d(inter/uni) + d(uni/hull)
@@ -203,7 +211,7 @@ __global__ __launch_bounds__(1024) void set_criterion_kernel(const SedtCriterion
       for (int bb = lane; bb < B; bb += 64) v += fabsf((float)card[d * B + bb] - a.tgt_len[bb]) / (float)B;
     }
     v = wave_sum(v);
-    if (lane == 0) sums[d][k] = v;
+    if (lane == 0) sums[d][k] = (k == 1 || k == 2) ? v + z : v;
   }
   __syncthreads();
   float total = 0.f;
