@@ -35,6 +35,8 @@
  *                                                                             utilities/BoxEncoder.py:179-226, engine.py:218-297
  *   sedt_psds_update                                                          PSDS confusion counts from those event records
  *                                                                             utilities/metrics.py:120-145, 325-330 (psds_eval)
+ *   sedt_stitch_events                                                        no counterpart (the reference scores 10 s clips only):
+ *                                                                             the windows' event records -> one list per recording
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -841,6 +843,38 @@ int sedt_psds_update(const int32_t* records, const int32_t* clip_idx, const int3
                      const int32_t* ref_cls, const double* ref_on, const double* ref_end, const double* ref_dur, int n_clips,
                      int max_ref, int B, int Q, int C, int K, int n_fusion, int fusion, double dtc, double gtc, double cttc,
                      int64_t* counts, void* stream);
+
+/* sedt_stitch_events (no counterpart in the reference, which scores 10 s dataset clips only; DESIGN.md section 4, "Recordings of any
+ * length", holds the definition and tests/recording_ref.py restates it): the event records of the overlapping windows of R recordings
+ * merged into one event list per (threshold, recording, class) - an event a window boundary cut in two, or one that two overlapping
+ * windows both report, becomes one event.  One wave per (recording, threshold) sweeps the windows in start order with the open merged
+ * events in LDS, so a recording may have any number of windows.
+ * records [K][W_stride][1 + 5 Q]: sedt_decode_events' words, one row per window (rows W .. W_stride - 1 are not read); win_off [R + 1]
+ * int32: recording r owns the windows win_off[r] .. win_off[r + 1] - 1, ascending by start; win_start [W] float64 seconds; rec_dur [R]
+ * float64 seconds (finite); merge_gap float64 >= 0; cap >= 1: the events per (threshold, recording, class) that `out` holds.
+ * Per threshold k, recording r, class c; float64 on the records' f32 values widened, plain adds and compares, no contraction:
+ *   candidates  every live slot s < n_w of every window w of r whose class is c.  A record whose count is outside 0 .. Q is skipped
+ *               whole, a slot whose class is outside 0 .. C - 1 or whose score is NaN is skipped; none is ever used as an index.
+ *               on = min(t_w + on32, rec_dur[r]), off = min(t_w + off32, rec_dur[r]), min(a, b) = a > b ? b : a; a candidate whose
+ *               off - on is not > 0 is dropped.
+ *   merging     the candidates in (on, w, s) order, swept: the running event starts as the first; a candidate with on <= cur.off +
+ *               merge_gap joins it (cur.off = max(cur.off, off), cur.n += 1, a STRICTLY higher score takes over cur.score, cur.window -
+ *               the index inside the recording - and cur.query), any other closes it and becomes the running event.
+ * count [K][R][C] int32: the number of merged events; it keeps counting past cap.
+ * out [K][R][C][cap][8 words] {onset f64, offset f64, score f32, n_merged int32, window int32, query int32}, ascending by onset; the
+ *   slots at or past min(count, cap) are left untouched.  8-byte aligned.
+ * status [K][R] int32, 0 or ONE of: 1 win_start of the recording not ascending (or NaN); 2 at some window w the merged events of the
+ *   windows before w that are still open (off + merge_gap >= t_w) plus the kept candidates of w exceed the kernel's working set of 640
+ *   (inside the envelope below it cannot happen); 4 a kept candidate with on < t_w (a negative onset in a record); 8 win_off[r] ..
+ *   win_off[r + 1] is not a range inside 0 .. W.  Checked in the order 8, 1, then window by window 4 before 2; the sweep stops at the
+ *   first.  With a status raised the recording's lists are not to be used: count reads 0 for every class.  Nothing is written out of
+ *   bounds in any case.
+ * Plain stores and integer LDS adds only: bit-reproducible, independent of launch order.
+ * 1 <= Q <= 64, 1 <= C <= 63, 1 <= K <= 1024, R >= 0 (R == 0 launches nothing), 0 <= W <= W_stride.  Envelope of status 2: at most 8
+ * earlier windows w' with t_w' + window + merge_gap >= t_w for records whose offsets are clipped to the window length. */
+int sedt_stitch_events(const int32_t* records, const int32_t* win_off, const double* win_start, const double* rec_dur, int K, int W,
+                       int W_stride, int R, int Q, int C, double merge_gap, int cap, int32_t* count, int32_t* out, int32_t* status,
+                       void* stream);
 
 /* ------------------------------------------------------------------ input side on the device (utilities/BoxTransforms.py,
  * utilities/mixup.py)

@@ -864,6 +864,69 @@ class GraphedPredictStep(object):
         return self.out
 
 
+# ---------------------------------------------------------------------------------------------------- detection without targets
+def detect_step(model, postprocessor, batch_input, sizes, fusion_strategy=(1,), at=True, threshold=0.5, decoder=None):
+    """predict_step without the criterion and the metrics, for audio that has no labels: no-grad forward, the thresholded audio tags,
+    ``postprocessor.batched`` once per fusion strategy (``sizes``: the clips' durations in seconds, f32 [B] on the device) and
+    ``decoder.decode``.  The same kernels in the same order as predict_step's, so on the same batch the tags, the PostProcess tensors
+    and the packed records are bit-identical to its.  Returns (audio_tags or None, {at_m: (scores, labels, boxes)}, decoded):
+    ``decoded`` is what decoder.decode returned - the static device buffers of this batch shape, nothing is copied to the host
+    (``decoder.fetch(decoded)`` does that) - or None without a decoder."""
+    with torch.no_grad():
+        outputs = model(batch_input)
+        audio_tags = (outputs['at'] > 0.5).long() if at else None
+        if at:
+            assert 'at' in outputs
+        results = {m: postprocessor.batched(outputs, sizes, audio_tags=audio_tags, at_m=m, threshold=threshold) for m in fusion_strategy}
+        decoded = None
+        if decoder is not None:
+            _check_decoder(decoder, fusion_strategy)
+            decoded = decoder.decode(results, audio_tags)
+    return audio_tags, results, decoded
+
+
+class GraphedDetectStep(object):
+    """detect_step as ONE HIP graph with a static input and static record buffers, warmed up and captured on the training stream like
+    GraphedPredictStep.  ``__call__(batch_input)`` copies the batch into ``static_x`` (None: the caller has written static_x itself, as
+    utilities.recording.RecordingDetector's front end does) and replays; the outputs are static tensors, overwritten by the next
+    call.  ``decoder.set_thresholds`` is followed by the next replay."""
+
+    def __init__(self, model, postprocessor, example_input, sizes, fusion_strategy=(1,), at=True, threshold=0.5, decoder=None, warmup=2):
+        self.model, self.post, self.decoder = model, postprocessor, decoder
+        self.fusion, self.at, self.threshold = tuple(fusion_strategy), at, threshold
+        dev = example_input.device
+        self.static_x = example_input.clone()
+        self.sizes = sizes.to(dev).float().clone()
+        if decoder is not None:
+            _check_decoder(decoder, self.fusion)
+        _warm_on_train_stream(dev, self._body, warmup)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=train_stream(dev), **_CAPTURE):
+            self.out = self._body()
+        torch.cuda.synchronize()
+
+    def _body(self):
+        return detect_step(self.model, self.post, self.static_x, self.sizes, self.fusion, self.at, self.threshold, self.decoder)
+
+    def __call__(self, batch_input=None, sizes=None):
+        if batch_input is not None:
+            self.static_x.copy_(batch_input, non_blocking=True)
+        if sizes is not None:
+            self.sizes.copy_(sizes, non_blocking=True)
+        self.graph.replay()
+        return self.out
+
+
+def detect_recordings(model, postprocessor, decoder, mel, transform, waves, filenames, window_seconds, hop_seconds, batch_windows=8,
+                      merge_gap=0.0, cap=None, at=True, threshold=0.5, graphed=True):
+    """the events of recordings of any length in one call: utilities.recording.RecordingDetector built and called once.  Returns
+    ({at_m: RecordingPredictions}, WindowTags).  Keep the detector yourself to replay its graph over many calls."""
+    from .utilities.recording import RecordingDetector
+    det = RecordingDetector(model, postprocessor, decoder, mel, transform, window_seconds, hop_seconds, batch_windows=batch_windows,
+                            merge_gap=merge_gap, cap=cap, at=at, threshold=threshold, graphed=graphed)
+    return det(waves, filenames)
+
+
 def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, threshold=0.5, graphed=True, max_targets=32):
     """engine.evaluate (engine.py:199-216) without leaving the device: ``batches`` yields (input, targets, clip indices into the
     metrics' reference) - the reference's data_prefetcher gives ((input, targets), indexes).  The counters are reset, every batch

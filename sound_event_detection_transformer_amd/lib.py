@@ -224,6 +224,7 @@ SIGNATURES = {
                                                _d, _i, _i, _vp, _vp, _d, _i, _vp, _vp, _vp]),
     'sedt_decode_events': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _d, _i, _vp, _vp]),
     'sedt_psds_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp]),
+    'sedt_stitch_events': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp]),
     'sedt_hungarian_batch': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'sedt_adamw_clip': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _i, _vp]),
 }

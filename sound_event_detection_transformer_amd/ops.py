@@ -1936,6 +1936,47 @@ def psds_update(records, clip_idx, table, n_clips, max_ref, n_classes, counts, f
                                       float(dtc), float(gtc), float(cttc), _p(counts), L.stream_ptr()), 'psds_update')
 
 
+STITCH_MAX_DEPTH = 8              # csrc/stitch.hip: earlier windows that may still be open when a window is reached
+STITCH_WORDS = 8                  # words of one stitched event {onset f64, offset f64, score f32, n_merged, window, query}
+
+
+def stitch_events_views(out):
+    """typed views on a stitched event buffer [K, R, C, cap, 8] (int32; a device tensor, a host tensor or a numpy array alike):
+    (times [K,R,C,cap,2] f64 {onset, offset}, score [K,R,C,cap] f32, n_merged, window, query [K,R,C,cap] int32)"""
+    f32, f64 = (torch.float32, torch.float64) if torch.is_tensor(out) else (np.float32, np.float64)
+    return out[..., 0:4].view(f64), out[..., 4].view(f32), out[..., 5], out[..., 6], out[..., 7]
+
+
+def stitch_events(records, win_off, win_start, rec_dur, n_classes, merge_gap=0.0, cap=64, n_windows=None, out=None, count=None,
+                  status=None):
+    """the event records of the overlapping windows of R recordings (``records``: int32 [K, W_stride, 1 + 5 Q], decode_events' words,
+    one row per window) merged into one event list per (threshold, recording, class): include/sedt_hip.h: sedt_stitch_events.
+    win_off int32 [R + 1], win_start float64 [W], rec_dur float64 [R] on the device; n_windows: W (else W_stride).  Returns
+    (count [K,R,C] int32, out [K,R,C,cap,8] int32, status [K,R] int32); ``out`` is left untouched past min(count, cap), so pass one
+    that is filled with what those slots should read."""
+    _dev_check(records, win_off, win_start, rec_dur, out, count, status)
+    K, Ws = records.shape[0], records.shape[1]
+    Q = (records.shape[2] - 1) // 5
+    C, R = int(n_classes), win_off.numel() - 1
+    W = Ws if n_windows is None else int(n_windows)
+    assert records.dtype == torch.int32 and records.dim() == 3 and records.shape[2] == 1 + 5 * Q and records.is_contiguous()
+    assert win_off.dtype == torch.int32 and win_off.dim() == 1 and R >= 0 and win_off.is_contiguous()
+    assert win_start.dtype == torch.float64 and win_start.numel() >= W and win_start.is_contiguous()
+    assert rec_dur.dtype == torch.float64 and rec_dur.numel() >= R and rec_dur.is_contiguous()
+    if out is None:
+        out = torch.zeros((K, R, C, int(cap), STITCH_WORDS), device=records.device, dtype=torch.int32)
+    if count is None:
+        count = torch.empty((K, R, C), device=records.device, dtype=torch.int32)
+    if status is None:
+        status = torch.empty((K, R), device=records.device, dtype=torch.int32)
+    assert out.dtype == torch.int32 and tuple(out.shape) == (K, R, C, int(cap), STITCH_WORDS) and out.is_contiguous()
+    assert count.dtype == torch.int32 and tuple(count.shape) == (K, R, C) and count.is_contiguous()
+    assert status.dtype == torch.int32 and tuple(status.shape) == (K, R) and status.is_contiguous()
+    L.check(L.load().sedt_stitch_events(_p(records), _p(win_off), _p(win_start), _p(rec_dur), K, W, Ws, R, Q, C, float(merge_gap), int(cap),
+                                        _p(count), _p(out), _p(status), L.stream_ptr()), 'stitch_events')
+    return count, out, status
+
+
 def mixup(x1, x2, jobs, out=None):
     """feature half of utilities/mixup.py: out[i] = lam * x1[src1] + (1 - lam) * x2[src2] / x1[src1] / x2[src2] per job record
     (jobs: uint8 device tensor of n 16-byte records {int32 src1, src2, mode; f32 lam}); x1 / x2 / out f32 [*, clip...]"""
