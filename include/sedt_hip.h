@@ -33,6 +33,10 @@
  *   sedt_event_segment_metrics_update                                         + sed_eval segment-based counts  utilities/metrics.py:83-116
  *   sedt_decode_events                                                        decode_strong + the clip, written out as event records
  *                                                                             utilities/BoxEncoder.py:179-226, engine.py:218-297
+ *   sedt_decode_events_classwise                                              the same with one threshold per class (the reference's
+ *                                                                             classwise_threshold, engine.py:300-348, applied to decode_strong)
+ *   sedt_event_sweep_update                                                   sed_eval event-based / clip-level counts at every operating
+ *                                                                             point, from those event records  utilities/metrics.py:43-80, 281-322
  *   sedt_psds_update                                                          PSDS confusion counts from those event records
  *                                                                             utilities/metrics.py:120-145, 325-330 (psds_eval)
  *   sedt_stitch_events                                                        no counterpart (the reference scores 10 s clips only):
@@ -820,6 +824,40 @@ int sedt_event_segment_metrics_update(const float* scores, const int64_t* labels
  * Q <= 64, C <= 63. */
 int sedt_decode_events(const float* scores, const int64_t* labels, const float* boxes, const float* thresholds, int B, int Q, int C,
                        int K, float min_duration, double max_len, int del_overlap, int32_t* out, void* stream);
+/* sedt_decode_events_classwise: the same kernel, the same arguments and the same records, with thresholds [K][C] f32 (a DEVICE table
+ * read by every launch): operating point k compares a query with thresholds[k][label] - the reference's classwise_threshold
+ * (engine.py:300-348 applies one per class to its pseudo labels; utilities/metrics.py get_f_measure_by_class takes thresholds_ per
+ * class) applied to decode_strong.  The label is tested against 0 <= label < C BEFORE the lookup: a query with any other label (-1, C,
+ * 2^40) is dropped and reads nothing.  Decode is class by class, so the events of class c at operating point k are those
+ * sedt_decode_events gives at the uniform threshold thresholds[k][c]; a table whose rows are constant gives records bit-identical
+ * to sedt_decode_events at that [K] grid. */
+int sedt_decode_events_classwise(const float* scores, const int64_t* labels, const float* boxes, const float* thresholds, int B,
+                                 int Q, int C, int K, float min_duration, double max_len, int del_overlap, int32_t* out, void* stream);
+
+/* sedt_event_sweep_update (utilities/metrics.py:43-80, 281-322 at every operating point): the event-based and clip-level counts of
+ * sedt_event_metrics_update for every threshold of the decoder's grid in one launch, from the buffer sedt_decode_events(_classwise)
+ * just wrote.  One wave per (clip, threshold); the decode is not repeated and the records' times, already clipped to [0, max_len], are
+ * not clipped again.
+ * records [K][B][1 + 5 Q]: sedt_decode_events' `out`.  A record whose count is outside 0 .. Q is skipped whole; a live slot whose class
+ * is outside 0 .. C - 1 is not counted; neither is ever used as an index.
+ * Reference table: sedt_event_metrics_update's (ref_present, ref_off, ref_cls, ref_on, ref_end, n_clips, max_ref <= 64, clip_idx with
+ * the same rule: -1, an index >= n_clips or ref_present 0 = a clip outside the table).
+ * Per clip and threshold, exactly sedt_event_metrics_update's counting on the record's events: a hit is an estimate of the reference
+ * event's class with |on_r - on_e| <= t_collar and |off_r - off_e| <= max(t_collar, pct * (off_r - on_r)), in float64 on the record's
+ * f32 times widened, no contraction; class-wise tp is the size of a maximum-cardinality matching of hits (optimal != 0) or of
+ * sed_eval's greedy pass (optimal == 0: references in table order, each takes the first free estimate of its class in record order).
+ * Counters (int64, integer atomics only; zero them per validation set):
+ *   ev_counts  [n_fusion][K][C][3] += {tp, n_ref, n_sys} at row `fusion`, from clips in the table only;
+ *   tag_counts [n_fusion][K][C][3] += {tp, fp, fn} of "class among the record's events" vs "class among the reference events" at row
+ *   `fusion`, from every clip: a clip outside the table has no reference events, so its classes count as false positives.
+ * At threshold k both equal what sedt_event_metrics_update counts at thresholds[k] on the same PostProcess outputs (decode and
+ * matching are class by class: under sedt_decode_events_classwise the counts of class c are those at the uniform threshold
+ * thresholds[k][c]).
+ * 1 <= Q <= 64, 1 <= C <= 63, 1 <= K <= 1024, max_ref <= 64, B >= 0 (B == 0 launches nothing). */
+int sedt_event_sweep_update(const int32_t* records, const int32_t* clip_idx, const int32_t* ref_present, const int32_t* ref_off,
+                            const int32_t* ref_cls, const double* ref_on, const double* ref_end, int n_clips, int max_ref, int B, int Q,
+                            int C, int K, int n_fusion, int fusion, double t_collar, double pct, int optimal, int64_t* ev_counts,
+                            int64_t* tag_counts, void* stream);
 
 /* sedt_psds_update (utilities/metrics.py:120-145, 325-330: psds_eval's PSDSEval restated, utilities/psds.py holds the definition): the
  * per-operating-point confusion counts of the polyphonic sound detection score, from the buffer sedt_decode_events just wrote.  One

@@ -23,12 +23,14 @@ namespace sedt {
 //   at or past n hold {-1, 0, 0, 0, -1}
 __global__ __launch_bounds__(64) void decode_events_kernel(const float* __restrict__ scores, const int64_t* __restrict__ labels,
                                                            const float* __restrict__ boxes, const float* __restrict__ thresholds,
-                                                           int B, int Q, int C, float min_dur, float max_len, int del_overlap,
-                                                           int32_t* __restrict__ out) {
+                                                           int class_wise, int B, int Q, int C, float min_dur, float max_len,
+                                                           int del_overlap, int32_t* __restrict__ out) {
   __shared__ float s_on[SEDT_DE_MAXQ], s_end[SEDT_DE_MAXQ], s_score[SEDT_DE_MAXQ];
   __shared__ int s_lab[SEDT_DE_MAXQ], s_surv[SEDT_DE_MAXQ], s_order[SEDT_DE_MAXQ];
   const int b = blockIdx.x, kt = blockIdx.y, lane = threadIdx.x;
-  const float threshold = thresholds[kt];                              // read on every launch: a captured graph follows an edited grid
+  // read on every launch: a captured graph follows an edited grid.  thresholds [K] (class_wise 0: one per operating point) or [K][C]
+  // (one per operating point and class, looked up by the query's label once that is known to be a class)
+  const float uniform = class_wise ? 0.f : thresholds[kt];
 
   // ---- decode_strong: keep (BoxEncoder.py:190-196 / :202-205)
   float on = 0.f, end = 0.f, sc = -INFINITY;
@@ -40,8 +42,10 @@ __global__ __launch_bounds__(64) void decode_events_kernel(const float* __restri
     const int64_t l = labels[r];
     on = boxes[2 * r];
     end = boxes[2 * r + 1];
+    const bool is_class = l >= 0 && l < C;                             // tested before the lookup: any other label reads nothing
+    const float threshold = !class_wise ? uniform : is_class ? thresholds[(long)kt * C + l] : INFINITY;
     const bool pass = del_overlap ? (sc >= threshold) : (sc > threshold);
-    keep = pass && (end - on) >= min_dur && l >= 0 && l < C;
+    keep = pass && (end - on) >= min_dur && is_class;
     lab = keep ? (int)l : -1;
   }
   // ---- order: with del_overlap (class by its first kept query - the reference's dict insertion order -, onset, query), else query.
@@ -115,17 +119,34 @@ __global__ __launch_bounds__(64) void decode_events_kernel(const float* __restri
 
 }  // namespace sedt
 
-extern "C" int sedt_decode_events(const float* scores, const int64_t* labels, const float* boxes, const float* thresholds, int B, int Q,
-                                  int C, int K, float min_duration, double max_len, int del_overlap, int32_t* out, void* stream) {
-  using namespace sedt;
-  SEDT_REQUIRE(scores && labels && boxes && thresholds && out, "decode_events: null pointer");
-  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_DE_MAXQ && C >= 1 && C <= SEDT_DE_MAXC, "decode_events: B=%d Q=%d (<=%d) C=%d (<=%d)", B, Q,
+namespace sedt {
+
+int decode_events_launch(const char* what, const float* scores, const int64_t* labels, const float* boxes, const float* thresholds,
+                         int class_wise, int B, int Q, int C, int K, float min_duration, double max_len, int del_overlap, int32_t* out,
+                         void* stream) {
+  SEDT_REQUIRE(scores && labels && boxes && thresholds && out, "%s: null pointer", what);
+  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_DE_MAXQ && C >= 1 && C <= SEDT_DE_MAXC, "%s: B=%d Q=%d (<=%d) C=%d (<=%d)", what, B, Q,
                SEDT_DE_MAXQ, C, SEDT_DE_MAXC);
-  SEDT_REQUIRE(K >= 1 && K <= SEDT_DE_MAXK, "decode_events: %d thresholds (1 .. %d)", K, SEDT_DE_MAXK);
+  SEDT_REQUIRE(K >= 1 && K <= SEDT_DE_MAXK, "%s: %d thresholds (1 .. %d)", what, K, SEDT_DE_MAXK);
   SEDT_REQUIRE(max_len >= 0.0 && (double)(float)max_len == max_len,
-               "decode_events: max_len %.17g is not a non-negative number float32 represents exactly (+inf: no clip)", max_len);
+               "%s: max_len %.17g is not a non-negative number float32 represents exactly (+inf: no clip)", what, max_len);
   if (B == 0) return 0;
   hipLaunchKernelGGL(decode_events_kernel, dim3(B, K), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), scores, labels, boxes,
-                     thresholds, B, Q, C, min_duration, (float)max_len, del_overlap, out);
-  return check_launch("decode_events");
+                     thresholds, class_wise, B, Q, C, min_duration, (float)max_len, del_overlap, out);
+  return check_launch(what);
+}
+
+}  // namespace sedt
+
+extern "C" int sedt_decode_events(const float* scores, const int64_t* labels, const float* boxes, const float* thresholds, int B, int Q,
+                                  int C, int K, float min_duration, double max_len, int del_overlap, int32_t* out, void* stream) {
+  return sedt::decode_events_launch("decode_events", scores, labels, boxes, thresholds, 0, B, Q, C, K, min_duration, max_len, del_overlap,
+                                    out, stream);
+}
+
+extern "C" int sedt_decode_events_classwise(const float* scores, const int64_t* labels, const float* boxes, const float* thresholds,
+                                            int B, int Q, int C, int K, float min_duration, double max_len, int del_overlap, int32_t* out,
+                                            void* stream) {
+  return sedt::decode_events_launch("decode_events_classwise", scores, labels, boxes, thresholds, 1, B, Q, C, K, min_duration, max_len,
+                                    del_overlap, out, stream);
 }

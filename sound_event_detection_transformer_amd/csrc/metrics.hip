@@ -9,6 +9,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "event_match.h"
 
 #pragma clang fp contract(off)     // the float64 collar tests must be the plain sub / mul / compare sed_eval evaluates
 
@@ -133,62 +134,14 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
   // estimates clipped to [0, max_len] (engine.py:287)
   const bool surv = lane < Q && s_surv[lane];
   const double my_on = fmin(fmax((double)on, 0.0), max_len), my_end = fmin(fmax((double)end, 0.0), max_len);
-  for (int j = 0; j < ne; ++j) {
-    const double ron = r_on[j], rend = r_end[j];
-    const double off_collar = fmax(t_collar, pct * (rend - ron));
-    const bool hit = surv && lab == r_cls[j] && fabs(ron - my_on) <= t_collar && fabs(rend - my_end) <= off_collar;
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) adj[j] = m;
-  }
+  event_hit_graph(adj, r_cls, r_on, r_end, ne, surv, lab, my_on, my_end, t_collar, pct, lane);
   __syncthreads();
 
-  // ---- per class: tp = maximum-cardinality matching (augmenting paths, breadth first) or sed_eval's greedy pass
+  // ---- per class: tp = maximum-cardinality matching (augmenting paths, breadth first) or sed_eval's greedy pass (event_match.h)
   long tp = 0, n_ref = 0, n_sys = 0;
   if (c < C) {
     for (int k = 0; k < n_c; ++k) n_sys += s_surv[s_order[start + k]];
-    for (int j = 0; j < ne; ++j) {
-      if (r_cls[j] != c) continue;
-      ++n_ref;
-      if (adj[j] == 0ull) continue;
-      if (optimal) {
-        unsigned char* qu = queue[c];
-        int head = 0, tail = 0, found = -1;
-        unsigned long long seen = 0ull;
-        qu[tail++] = (unsigned char)j;
-        while (head < tail && found < 0) {
-          const int r = qu[head++];
-          unsigned long long avail = adj[r] & ~seen;
-          while (avail) {
-            const int q = __ffsll((long long)avail) - 1;
-            avail &= avail - 1ull;
-            seen |= 1ull << q;
-            from_ref[q] = r;
-            if (match_est[q] < 0) { found = q; break; }
-            qu[tail++] = (unsigned char)match_est[q];    // each matched ref enters once: its estimate is seen once
-          }
-        }
-        if (found >= 0) {
-          int q = found;
-          for (;;) {                                      // flip the path back to j
-            const int r = from_ref[q], prev = match_ref[r];
-            match_ref[r] = q;
-            match_est[q] = r;
-            if (r == j) break;
-            q = prev;
-          }
-          ++tp;
-        }
-      } else {
-        for (int k = 0; k < n_c; ++k) {                   // estimates in their output order, first free hit wins
-          const int q = s_order[start + k];
-          if (s_surv[q] && match_est[q] < 0 && ((adj[j] >> q) & 1ull)) {
-            match_est[q] = j;
-            ++tp;
-            break;
-          }
-        }
-      }
-    }
+    tp = event_class_match(c, ne, r_cls, adj, match_est, from_ref, match_ref, queue[c], optimal, s_order + start, n_c, n_ref);
     if (clip >= 0) {
       unsigned long long* e = ev + ((long)fusion * C + c) * 3;
       if (tp) atomicAdd(e, (unsigned long long)tp);

@@ -722,7 +722,7 @@ def _tensors(x):
 
 # ---------------------------------------------------------------------------------------------------- validation / prediction
 def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_strategy=(1,), at=True, threshold=0.5, metrics=None,
-                 clip_idx=None, decoder=None, psds=None):
+                 clip_idx=None, decoder=None, psds=None, sweep=None):
     """The per-batch body of reference engine.get_sedt_predictions (engine.py:244-285) on the device: no-grad forward, the
     losses the reference logs (criterion with strong_mask = the whole batch), the thresholded audio tags, and
     ``postprocessors['bbox']`` once per fusion strategy.  Returns (loss_dict, audio_tags or None, {at_m: (scores [B,Q], labels
@@ -733,11 +733,16 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
     is enqueued: a fourth value is returned, the handle whose ``rows()`` waits for the copy and unpacks.  Without either, the
     decoding into event lists stays the caller's, as in the reference.  With ``psds`` (utilities.psds.PsdsMetrics, bound to this
     ``decoder``) the PSDS confusion counts of the batch's records (clips ``clip_idx`` of its reference) are added on the device by the
-    launch after the decode's."""
+    launch after the decode's.  With ``sweep`` (utilities.operating_points.SweepEventMetrics, bound to this ``decoder``) the event-based
+    and clip-level counts of the batch's records at every threshold of the grid are added on the device in the same way."""
     if psds is not None:
         _check_psds(psds, decoder)
         if clip_idx is None:
             raise ValueError('predict_step(psds=...) needs the clip indices of the batch (clip_idx)')
+    if sweep is not None:
+        _check_sweep(sweep, decoder)
+        if clip_idx is None:
+            raise ValueError('predict_step(sweep=...) needs the clip indices of the batch (clip_idx)')
     with torch.no_grad():
         outputs = model(batch_input)
         B = outputs['pred_logits'].shape[0]
@@ -757,6 +762,8 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
             decoded = decoder.decode(results, audio_tags)
             if psds is not None:
                 psds.update(decoded, clip_idx)
+            if sweep is not None:
+                sweep.update(decoded, clip_idx)
             return loss_dict, audio_tags, results, decoder.fetch()
     return loss_dict, audio_tags, results
 
@@ -776,6 +783,11 @@ def _check_psds(psds, decoder):
         raise ValueError('psds= scores the event records of the EventDecoder it was built with: pass that decoder as decoder=')
 
 
+def _check_sweep(sweep, decoder):
+    if decoder is None or sweep.decoder is not decoder:
+        raise ValueError('sweep= scores the event records of the EventDecoder it was built with: pass that decoder as decoder=')
+
+
 class GraphedPredictStep(object):
     """predict_step as ONE HIP graph (forward, device Hungarian matching + fused losses for the logged validation losses, audio
     tags, PostProcess for every fusion strategy): per batch the host refreshes the static input / target tables and replays;
@@ -793,10 +805,14 @@ class GraphedPredictStep(object):
 
     ``psds`` (utilities.psds.PsdsMetrics, bound to ``decoder``, its reference set before the step is built): the launch after the
     decode's adds the PSDS confusion counts of the records to the psds' device counters; each call takes the batch's clip indices.
-    Building the step leaves the counters as they were."""
+    Building the step leaves the counters as they were.
+
+    ``sweep`` (utilities.operating_points.SweepEventMetrics, bound to ``decoder``, its reference set before the step is built): one
+    more launch after the decode's adds the event-based and clip-level counts of the records at every threshold of the grid to the
+    sweep's device counters, under the same rules as ``psds``."""
 
     def __init__(self, model, criterion, postprocessor, example_input, example_targets, fusion_strategy=(1,), at=True, threshold=0.5,
-                 max_targets=32, warmup=2, metrics=None, decoder=None, psds=None):
+                 max_targets=32, warmup=2, metrics=None, decoder=None, psds=None, sweep=None):
         from .sedt import TargetTables
         self.model, self.criterion, self.post = model, criterion, postprocessor
         self.fusion, self.at, self.threshold = tuple(fusion_strategy), at, threshold
@@ -805,17 +821,19 @@ class GraphedPredictStep(object):
         B = len(example_targets)
         self.tables = TargetTables(B, B, B, dev, max_targets=max_targets, with_ratio=False, weak_mask_none=True).load(example_targets)
         self.sizes = torch.stack([t['orig_size'] for t in example_targets], dim=0).to(dev).float().clone()
-        self.metrics, self.decoder, self.psds = metrics, decoder, psds
+        self.metrics, self.decoder, self.psds, self.sweep = metrics, decoder, psds, sweep
         if decoder is not None:
             _check_decoder(decoder, self.fusion)
         if psds is not None:
             _check_psds(psds, decoder)
-        self.counted = [m for m in (metrics, psds) if m is not None]   # what counts per clip: each takes the batch's clip indices
+        if sweep is not None:
+            _check_sweep(sweep, decoder)
+        self.counted = [m for m in (metrics, psds, sweep) if m is not None]   # what counts per clip: each takes the batch's clip indices
         for m in self.counted:
             if m is metrics:
                 _check_metrics(metrics, self.fusion)
             if m.table is None:
-                raise RuntimeError('GraphedPredictStep(metrics= / psds=...): call set_reference() on it before building the step')
+                raise RuntimeError('GraphedPredictStep(metrics= / psds= / sweep=...): call set_reference() on it before building the step')
         if self.counted:
             self.clip_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.counted_gen = [m.generation for m in self.counted]
@@ -844,6 +862,8 @@ class GraphedPredictStep(object):
                 self.decoded = self.decoder.decode(res, tags)           # the static buffers the captured launches fill
                 if self.psds is not None:
                     self.psds.update(self.decoded, self.clip_idx)
+                if self.sweep is not None:
+                    self.sweep.update(self.decoded, self.clip_idx)
         return losses, tags, res
 
     def __call__(self, batch_input, targets, clip_idx=None):
@@ -852,7 +872,7 @@ class GraphedPredictStep(object):
         self.sizes.copy_(torch.stack([t['orig_size'] for t in targets], dim=0), non_blocking=True)
         if self.counted:
             if clip_idx is None:
-                raise ValueError('GraphedPredictStep(metrics= / psds=...) needs the clip indices of the batch (clip_idx)')
+                raise ValueError('GraphedPredictStep(metrics= / psds= / sweep=...) needs the clip indices of the batch (clip_idx)')
             if [m.generation for m in self.counted] != self.counted_gen:
                 raise RuntimeError('GraphedPredictStep: the metrics\' reference changed shape after the step was built; build a new step')
             if not (torch.is_tensor(clip_idx) and clip_idx.is_cuda):
@@ -948,7 +968,7 @@ def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, 
 
 
 def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, filenames, at=True, graphed=True, metrics=None,
-                         max_targets=32, threshold=0.5, step=None, psds=None):
+                         max_targets=32, threshold=0.5, step=None, psds=None, sweep=None):
     """engine.get_sedt_predictions (engine.py:218-297) with the decode on the device: ``batches`` yields (input, targets, clip
     indices) as for evaluate_events, ``decoder`` is a utilities.predictions.EventDecoder and ``filenames`` the dataset's clip names
     (indexed by clip index).  Returns (audio-tag table, {at_m: PredictionSet}): the reference's audio_tag_dfs and dec_prediction_dfs,
@@ -958,7 +978,9 @@ def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, file
     resets and fills the counters: ``metrics.compute()`` afterwards gives evaluate_events' scores.  ``step``: a
     GraphedPredictStep built with this decoder (and these metrics and psds) to replay instead of capturing a new one, for a validation
     pass per epoch.  With ``psds`` (utilities.psds.PsdsMetrics bound to ``decoder``, its reference set) the same pass resets and fills
-    its counters: ``psds.compute()`` afterwards gives the PSD scores of the decoder's grid of operating points."""
+    its counters: ``psds.compute()`` afterwards gives the PSD scores of the decoder's grid of operating points.  With ``sweep``
+    (utilities.operating_points.SweepEventMetrics bound to ``decoder``, its reference set) likewise: ``sweep.compute()`` afterwards gives
+    the event-based and clip-level scores at every operating point (``tune_thresholds`` chooses thresholds from them)."""
     from .utilities import predictions as P
     fusion = decoder.fusion
     if metrics is not None:
@@ -967,20 +989,24 @@ def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, file
     if psds is not None:
         _check_psds(psds, decoder)
         psds.reset()
-    counted = metrics is not None or psds is not None
+    if sweep is not None:
+        _check_sweep(sweep, decoder)
+        sweep.reset()
+    counted = metrics is not None or psds is not None or sweep is not None
     tag_table, sets = P.TagTable(), decoder.prediction_sets()
-    if step is not None and (step.decoder is not decoder or step.metrics is not metrics or step.psds is not psds or step.fusion != fusion):
-        raise ValueError('get_sedt_predictions: the step was built with another decoder, metrics, psds or fusion strategy')
+    if step is not None and (step.decoder is not decoder or step.metrics is not metrics or step.psds is not psds
+                             or step.sweep is not sweep or step.fusion != fusion):
+        raise ValueError('get_sedt_predictions: the step was built with another decoder, metrics, psds, sweep or fusion strategy')
     pending = None
     for x, targets, idx in batches:
         if graphed and step is None:
             step = GraphedPredictStep(model, criterion, postprocessor, x, targets, fusion_strategy=fusion, at=at, threshold=threshold,
-                                      max_targets=max_targets, metrics=metrics, decoder=decoder, psds=psds)
+                                      max_targets=max_targets, metrics=metrics, decoder=decoder, psds=psds, sweep=sweep)
         if step is not None and x.shape == step.static_x.shape:
             fetched = step(x, targets, idx if counted else None)[3]
         else:
             fetched = predict_step(model, criterion, postprocessor, x, targets, fusion_strategy=fusion, at=at, threshold=threshold,
-                                   metrics=metrics, clip_idx=idx if counted else None, decoder=decoder, psds=psds)[3]
+                                   metrics=metrics, clip_idx=idx if counted else None, decoder=decoder, psds=psds, sweep=sweep)[3]
         names = [filenames[int(k)] for k in idx]
         if pending is not None:
             P.collect(*pending, tag_table, sets, decoder.labels)
@@ -988,6 +1014,25 @@ def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, file
     if pending is not None:
         P.collect(*pending, tag_table, sets, decoder.labels)
     return tag_table, sets
+
+
+class _ClipNames(object):
+    """filenames for a pass whose rows nobody reads: clip k is named by its index"""
+
+    def __getitem__(self, k):
+        return str(k)
+
+
+def tune_thresholds(model, criterion, postprocessor, batches, decoder, sweep, filenames=None, at=True, graphed=True, step=None):
+    """one decision threshold per class from ONE validation pass: ``batches`` as for get_sedt_predictions, ``decoder`` an EventDecoder
+    whose grid holds the candidate thresholds, ``sweep`` a utilities.operating_points.SweepEventMetrics bound to it, its reference set
+    (``step``: a GraphedPredictStep built with both, to replay).  The pass is get_sedt_predictions(sweep=...); returns {at_m:
+    sweep.compute()[at_m].best_class_wise()} - per fusion strategy {'index' [C], 'thresholds' [C], 'class_f1' [C], 'f1'}.  An
+    EventDecoder(class_wise=True) set to 'thresholds' delivers that macro F1 on the same set; ``sweep.compute()`` still holds the whole
+    F1-versus-threshold curve of every class."""
+    get_sedt_predictions(model, criterion, postprocessor, batches, decoder, _ClipNames() if filenames is None else filenames, at=at,
+                         graphed=graphed, step=step, sweep=sweep)
+    return {m: r.best_class_wise() for m, r in sweep.compute().items()}
 
 
 def pseudo_label_tables(tea_outputs, classwise_threshold, orig_size, tables, counter=None, del_overlap=True):

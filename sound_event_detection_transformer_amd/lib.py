@@ -223,6 +223,8 @@ SIGNATURES = {
     'sedt_event_segment_metrics_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _d, _d,
                                                _d, _i, _i, _vp, _vp, _d, _i, _vp, _vp, _vp]),
     'sedt_decode_events': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _d, _i, _vp, _vp]),
+    'sedt_decode_events_classwise': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _d, _i, _vp, _vp]),
+    'sedt_event_sweep_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),
     'sedt_psds_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp]),
     'sedt_stitch_events': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp]),
     'sedt_hungarian_batch': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -1897,21 +1897,48 @@ def decode_events_views(packed, Q):
 def decode_events(scores, labels, boxes, thresholds, n_classes, min_duration=0.2, max_len=10.0, del_overlap=True, out=None):
     """decode_strong + the clip to [0, max_len] of one fusion strategy's PostProcess outputs (scores [B,Q] f32, labels [B,Q] int64,
     boxes [B,Q,2] f32 seconds) at every threshold of the DEVICE f32 vector ``thresholds`` [K], written out as event records in the
-    reference's output order (include/sedt_hip.h: sedt_decode_events).  max_len: a value float32 holds exactly, inf = no clip.
-    Returns (packed, count, class, times, score, query): the int32 buffer [K, B, 1 + 5 Q] (``out`` when given) and
-    decode_events_views of it."""
+    reference's output order (include/sedt_hip.h: sedt_decode_events).  ``thresholds`` [K, C] holds one threshold per operating
+    point and class: a query is compared with the one of its label (sedt_decode_events_classwise).  max_len: a value float32 holds
+    exactly, inf = no clip.  Returns (packed, count, class, times, score, query): the int32 buffer [K, B, 1 + 5 Q] (``out`` when
+    given) and decode_events_views of it."""
     _dev_check(scores, labels, boxes, thresholds, out)
     B, Q = scores.shape
-    K = thresholds.numel()
+    K = thresholds.shape[0] if thresholds.dim() else 0
     assert scores.dtype == torch.float32 and labels.dtype == torch.int64 and boxes.dtype == torch.float32
     assert scores.is_contiguous() and labels.is_contiguous() and boxes.is_contiguous() and tuple(boxes.shape) == (B, Q, 2)
-    assert tuple(labels.shape) == (B, Q) and thresholds.dtype == torch.float32 and thresholds.dim() == 1 and thresholds.is_contiguous()
+    assert tuple(labels.shape) == (B, Q) and thresholds.dtype == torch.float32 and thresholds.is_contiguous()
+    assert thresholds.dim() == 1 or tuple(thresholds.shape) == (K, int(n_classes)), (tuple(thresholds.shape), n_classes)
     if out is None:
         out = torch.empty((K, B, 1 + 5 * Q), device=scores.device, dtype=torch.int32)
     assert out.dtype == torch.int32 and tuple(out.shape) == (K, B, 1 + 5 * Q) and out.is_contiguous()
-    L.check(L.load().sedt_decode_events(_p(scores), _p(labels), _p(boxes), _p(thresholds), B, Q, int(n_classes), K, float(min_duration),
-                                        float(max_len), int(bool(del_overlap)), _p(out), L.stream_ptr()), 'decode_events')
+    entry = L.load().sedt_decode_events if thresholds.dim() == 1 else L.load().sedt_decode_events_classwise
+    L.check(entry(_p(scores), _p(labels), _p(boxes), _p(thresholds), B, Q, int(n_classes), K, float(min_duration), float(max_len),
+                  int(bool(del_overlap)), _p(out), L.stream_ptr()), 'decode_events' if thresholds.dim() == 1 else 'decode_events_classwise')
     return (out,) + decode_events_views(out, Q)
+
+
+def event_sweep_update(records, clip_idx, table, n_clips, max_ref, n_classes, ev_counts, tag_counts, fusion, t_collar=0.2, pct=0.2,
+                       optimal=True):
+    """sed_eval's event-based and the clip-level counts of one fusion strategy's event records (``records``: the int32 buffer
+    [K, B, 1 + 5 Q] decode_events filled) at every threshold of the grid, accumulated into ev_counts / tag_counts int64
+    [n_fusion, K, C, 3] at row ``fusion`` (include/sedt_hip.h: sedt_event_sweep_update).  table: event_metrics_update's device
+    reference table; clip_idx int32 [B] (-1 = outside the table).  Nothing is decoded again and nothing is read back."""
+    _dev_check(records, clip_idx, ev_counts, tag_counts)
+    K, B = records.shape[0], records.shape[1]
+    C = int(n_classes)
+    Q = (records.shape[2] - 1) // 5
+    assert records.dtype == torch.int32 and records.dim() == 3 and records.shape[2] == 1 + 5 * Q and records.is_contiguous()
+    assert clip_idx.dtype == torch.int32 and clip_idx.numel() == B and clip_idx.is_contiguous()
+    nf = ev_counts.shape[0]
+    assert ev_counts.dtype == torch.int64 and tuple(ev_counts.shape) == (nf, K, C, 3) and ev_counts.is_contiguous()
+    assert tag_counts.dtype == torch.int64 and tuple(tag_counts.shape) == (nf, K, C, 3) and tag_counts.is_contiguous()
+    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_clips + 1
+    assert table['present'].dtype == torch.int32 and table['present'].numel() >= n_clips
+    assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
+    L.check(L.load().sedt_event_sweep_update(_p(records), _p(clip_idx), _p(table['present']), _p(table['off']), _p(table['cls']),
+                                             _p(table['on']), _p(table['end']), int(n_clips), int(max_ref), B, Q, C, K, nf, int(fusion),
+                                             float(t_collar), float(pct), int(bool(optimal)), _p(ev_counts), _p(tag_counts),
+                                             L.stream_ptr()), 'event_sweep_update')
 
 
 def psds_update(records, clip_idx, table, n_clips, max_ref, n_classes, counts, fusion, dtc=0.5, gtc=0.5, cttc=0.3):

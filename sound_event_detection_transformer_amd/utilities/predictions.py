@@ -20,6 +20,13 @@ COLUMNS = ('event_label', 'onset', 'offset', 'score', 'filename')      # the ref
 TAG_COLUMNS = ('event_label', 'filename', 'onset', 'offset')           # its audio-tag frame (engine.py:269-272)
 
 
+def operating_point(t):
+    """the threshold of one operating point as it is reported: a float, or with class-wise thresholds (one row of an EventDecoder's
+    [K, C] grid) a tuple of C floats"""
+    t = np.asarray(t)
+    return float(t) if t.ndim == 0 else tuple(float(v) for v in t.reshape(-1))
+
+
 def unpack(packed, Q):
     """a packed decode buffer [K, B, 1 + 5 Q] (numpy int32, include/sedt_hip.h: sedt_decode_events) -> per threshold a dict of
     copied arrays {clip int64 [n], cls int32 [n], onset / offset / score float32 [n], query int32 [n]}: clips in order, the events
@@ -38,7 +45,8 @@ def unpack(packed, Q):
 
 
 class PredictionTable(object):
-    """the prediction rows at one threshold as column arrays: event_label (names), onset, offset, score (float32), filename"""
+    """the prediction rows at one threshold (a float, or a tuple of one per class) as column arrays: event_label (names), onset, offset,
+    score (float32), filename"""
 
     def __init__(self, threshold, event_label, onset, offset, score, filename):
         self.threshold = threshold
@@ -64,12 +72,13 @@ class PredictionTable(object):
 
 
 class PredictionSet(object):
-    """one fusion strategy's predictions over a validation pass, per threshold of the decoder's grid.  Order is the reference's:
-    batches in order, clips in order, events in decode order."""
+    """one fusion strategy's predictions over a validation pass, per threshold of the decoder's grid (``thresholds``: per operating
+    point a float, or for a class-wise decoder the C thresholds of its classes, kept as a tuple).  Order is the reference's: batches in
+    order, clips in order, events in decode order."""
 
     def __init__(self, labels, thresholds):
         self.labels = np.asarray(list(labels), dtype=object)
-        self.thresholds = [float(t) for t in thresholds]
+        self.thresholds = [operating_point(t) for t in thresholds]
         self._parts = [[] for _ in self.thresholds]
         self._tables = None
 
@@ -166,10 +175,15 @@ class EventDecoder(object):
     """decode_strong(threshold, del_overlap) + the clip to [0, max_len_seconds] at every threshold of a grid, on the device.
     ``labels``: the class names in the model's class order (decoder.labels); ``max_len_seconds``: a value float32 holds exactly
     (the drivers' 10), inf for no clip; ``thresholds``: the grid (K values, compared as float32 like the reference's torch scalars);
-    ``fusion_strategy``: the PostProcess fusion modes the predict step runs, in its order."""
+    ``fusion_strategy``: the PostProcess fusion modes the predict step runs, in its order.
+
+    ``class_wise=True``: every operating point holds one threshold per class - the device grid and ``threshold_values`` are [K, C], a
+    query is compared with the threshold of its label, ``thresholds`` / ``set_thresholds`` take [K] (each value for every class) or
+    [K, C], and an operating point's threshold is reported as a tuple of C floats (``operating_points()``).  Decode is class by class:
+    class c's events at point k are those of a uniform threshold threshold_values[k, c]."""
 
     def __init__(self, labels, max_len_seconds, thresholds=(0.5,), min_duration=0.2, del_overlap=True, fusion_strategy=(1,), device=None,
-                 slots=2):
+                 slots=2, class_wise=False):
         self.labels = list(labels)
         self.C = len(self.labels)
         assert 1 <= self.C <= 63, 'EventDecoder: 1..63 classes'
@@ -179,9 +193,10 @@ class EventDecoder(object):
         self.min_duration, self.del_overlap = float(min_duration), bool(del_overlap)
         self.fusion = tuple(fusion_strategy)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.class_wise = bool(class_wise)
         host = self._grid(thresholds)
-        if not 1 <= host.size <= ops.DECODE_MAX_THRESHOLDS:
-            raise ValueError(f'EventDecoder: {host.size} thresholds (1 .. {ops.DECODE_MAX_THRESHOLDS})')
+        if not 1 <= host.shape[0] <= ops.DECODE_MAX_THRESHOLDS:
+            raise ValueError(f'EventDecoder: {host.shape[0]} thresholds (1 .. {ops.DECODE_MAX_THRESHOLDS})')
         self.threshold_values = host
         self.thresholds = torch.from_numpy(host.copy()).to(self.device)
         assert slots >= 2
@@ -190,22 +205,32 @@ class EventDecoder(object):
         self._last = None
         self._serial = 0
 
-    @staticmethod
-    def _grid(values):
-        host = np.asarray(list(values), dtype=np.float64).reshape(-1).astype(np.float32)
+    def _grid(self, values):
+        host = np.asarray(list(values), dtype=np.float64)
+        if not self.class_wise:
+            host = host.reshape(-1)
+        elif host.ndim <= 1:
+            host = np.repeat(host.reshape(-1, 1), self.C, axis=1)          # [K]: each value for every class
+        elif host.ndim != 2 or host.shape[1] != self.C:
+            raise ValueError(f'EventDecoder: class-wise thresholds {host.shape} are neither [K] nor [K, {self.C}]')
+        host = np.ascontiguousarray(host.astype(np.float32))
         if np.isnan(host).any():
             raise ValueError('EventDecoder: a threshold is NaN')
         return host
 
     @property
     def K(self):
-        return self.threshold_values.size
+        return self.threshold_values.shape[0]
+
+    def operating_points(self):
+        """the grid as it is reported: per operating point a float, or with class_wise a tuple of C floats"""
+        return [operating_point(t) for t in self.threshold_values]
 
     def set_thresholds(self, values):
-        """another grid of the same K, in place: a captured graph reads it at its next replay"""
+        """another grid of the same K ([K], or with class_wise [K] or [K, C]), in place: a captured graph reads it at its next replay"""
         host = self._grid(values)
-        if host.size != self.K:
-            raise ValueError(f'set_thresholds: {host.size} thresholds, the decoder was built with {self.K}')
+        if host.shape[0] != self.K:
+            raise ValueError(f'set_thresholds: {host.shape[0]} thresholds, the decoder was built with {self.K}')
         self.threshold_values = host
         self.thresholds.copy_(torch.from_numpy(host.copy()))
         return self

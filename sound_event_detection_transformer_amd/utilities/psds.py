@@ -121,7 +121,8 @@ def psds_from_counts(counts, n_gt, gt_dur, total_dur, alpha_ct=0, alpha_st=0, ma
 
 class PsdsResult(dict):
     """one fusion strategy's scores: {'psds': {(alpha_ct, alpha_st, max_efpr): value}, 'tpr' [K, C], 'fpr' [K, C] (per hour),
-    'ctr' [K, C, C] (per hour), 'thresholds' [K]}; ``curve(setting)`` gives the PSD-ROC of a setting"""
+    'ctr' [K, C, C] (per hour), 'thresholds' [K] (of a class-wise decoder: a tuple of C floats each)}; ``curve(setting)`` gives the
+    PSD-ROC of a setting"""
 
     def curve(self, setting=SETTINGS[0]):
         """(efpr, etpr): the common axis (per hour, not cut at max_efpr) and the effective true positive rate on it, a step function
@@ -249,7 +250,7 @@ class PsdsMetrics(object):
         for i, m in enumerate(self.fusion):
             tpr, fpr, ctr, valid = _rates(counts[i], self.n_gt, self.gt_dur, self.total_dur)
             r = PsdsResult(psds={tuple(s): _curve(tpr, fpr, ctr, valid, *s)[0] for s in settings}, tpr=tpr, fpr=fpr, ctr=ctr,
-                           thresholds=[float(t) for t in self.decoder.threshold_values])
+                           thresholds=self.decoder.operating_points())
             r._valid = valid
             res[m] = r
         return res

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .predictions import COLUMNS
+from .predictions import COLUMNS, operating_point
 from .transforms import PinnedRing
 
 MAX_OUTPUT_BYTES = 1 << 30        # the stitched event buffer of one fusion strategy
@@ -88,7 +88,7 @@ class RecordingPredictions(object):
 
     def __init__(self, labels, thresholds, filenames, count, out, status, cap):
         self.labels = np.asarray(list(labels), dtype=object)
-        self.thresholds = [float(t) for t in thresholds]
+        self.thresholds = [operating_point(t) for t in thresholds]
         self.filenames = np.asarray(list(filenames), dtype=object)
         count, status = np.asarray(count), np.asarray(status)
         K, R, C = count.shape
