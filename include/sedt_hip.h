@@ -1007,6 +1007,30 @@ int sedt_mel_ok(int n_fft, int n_window, int hop, int n_mels);
 int sedt_mel_spectrogram(const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* nsamples, int B, float* out,
                          int out_rows, const float* window, const float* twiddle, const int32_t* band_bin0, const int32_t* band_off,
                          const float* band_w, int n_weights, int n_fft, int n_window, int hop, int n_mels, void* stream);
+/* sedt_resample: sample-rate conversion L / M = target / source rate (lowest terms) and down-mix of a batch of recordings that share
+ * (L, M, taps, H, table), in ONE launch - band-limited interpolation with a Kaiser-windowed sinc in its polyphase form (definition:
+ * utilities/resample.py).  For recording b with n_in frames, n_out = min(ceil(n_in L / M), cap), computed in 64-bit integers:
+ *   y[n] = sum over k = -H .. taps - 1 - H, ascending, of T[(n M) mod L][k] * m[(n M) div L + k],   n = 0 .. n_out - 1,
+ *   m[j] = the mean over the channels of frame j (summed in float64, rounded once; one channel: the sample itself), 0 outside
+ *   0 <= j < n_in - no reflection; dst[n_out .. cap - 1] is written as 0.
+ * One f32 product, then fmaf in that order: an output's bits depend on its recording, n and the table alone - not on B, on the
+ * recording's place in the batch, on cap or on how outputs fall into workgroups (SEDT_RESAMPLE_BLK consecutive outputs each).
+ * desc: DEVICE memory, int64 [B][SEDT_RESAMPLE_DESC_WORDS] = {source address, destination address (f32), n_in, cap, channels,
+ * dtype (SEDT_F32, or SEDT_I16: a sample is worth x / 32768)}; the source is interleaved (frames, channels) and holds n_in * channels
+ * elements, the destination cap floats - so results can go straight into one flat vector at chosen offsets.  The kernel clamps n_in
+ * to 0 .. max_in and channels to 1 .. max_channels, the bounds the caller declares.  max_out: the largest cap of the batch (it sizes
+ * the grid).  table: DEVICE f32 [taps][L], line k + H holding tap k, column r holding phase (r M) mod L (utilities/resample.py
+ * device_table: lanes that own consecutive outputs read consecutive floats); made on the host in float64 and rounded once - the
+ * kernel evaluates no Bessel function and no sine.  The identity plan is L = M = taps = 1, H = 0, table {1}: a mono f32 source comes
+ * out bit for bit.  No allocation, no synchronisation, no atomics; capturable.
+ * Envelope (sedt_resample_ok, 1 = inside): 1 <= L, M <= 4096; 1 <= taps <= 8192; 0 <= H < taps; L * taps * 4 <= 16 MiB of table;
+ * ceil(SEDT_RESAMPLE_BLK * M / L) + taps + 1 <= 16384 floats of LDS; 1 <= max_channels <= 64; 1 <= max_in <= 2^40.  Outside it, or
+ * with B > 65535 or a null pointer, sedt_resample returns non-zero with a message before it touches a pointer. */
+#define SEDT_RESAMPLE_BLK 1024
+#define SEDT_RESAMPLE_DESC_WORDS 6
+int sedt_resample_ok(int L, int M, int taps, int H, int max_channels, int64_t max_in);
+int sedt_resample(const int64_t* desc, int B, int64_t max_out, const float* table, int L, int M, int taps, int H, int max_channels,
+                  int64_t max_in, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

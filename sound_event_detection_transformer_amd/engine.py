@@ -938,13 +938,15 @@ class GraphedDetectStep(object):
 
 
 def detect_recordings(model, postprocessor, decoder, mel, transform, waves, filenames, window_seconds, hop_seconds, batch_windows=8,
-                      merge_gap=0.0, cap=None, at=True, threshold=0.5, graphed=True):
+                      merge_gap=0.0, cap=None, at=True, threshold=0.5, graphed=True, sample_rates=None, resample_quality='kaiser_best'):
     """the events of recordings of any length in one call: utilities.recording.RecordingDetector built and called once.  Returns
-    ({at_m: RecordingPredictions}, WindowTags).  Keep the detector yourself to replay its graph over many calls."""
+    ({at_m: RecordingPredictions}, WindowTags).  Keep the detector yourself to replay its graph over many calls.  ``sample_rates``
+    (one int or one per recording): the recordings' own rates; they are down-mixed and resampled to mel.sr on the device."""
     from .utilities.recording import RecordingDetector
     det = RecordingDetector(model, postprocessor, decoder, mel, transform, window_seconds, hop_seconds, batch_windows=batch_windows,
-                            merge_gap=merge_gap, cap=cap, at=at, threshold=threshold, graphed=graphed)
-    return det(waves, filenames)
+                            merge_gap=merge_gap, cap=cap, at=at, threshold=threshold, graphed=graphed,
+                            resample_quality=resample_quality)
+    return det(waves, filenames, sample_rates)
 
 
 def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, threshold=0.5, graphed=True, max_targets=32):

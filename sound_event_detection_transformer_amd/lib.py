@@ -13,7 +13,9 @@ if os.environ.get('SEDT_LIB_AB') and os.environ.get('SEDT_DEV') == '1':   # deve
 
 F32, BF16 = 0, 1
 BF16X3 = 2            # GEMM entry points only: f32 tensors, split-bf16 products (include/sedt_hip.h)
-I16 = 3               # sedt_mel_spectrogram only: the waveform as 16-bit PCM
+I16 = 3               # sedt_mel_spectrogram and sedt_resample only: the waveform as 16-bit PCM
+RESAMPLE_BLK = 1024   # sedt_resample: outputs per workgroup (SEDT_RESAMPLE_BLK)
+RESAMPLE_DESC_WORDS = 6
 GEMM_X3 = False       # runtime.set_compute_dtype('bf16x3'): the f32 mode's contractions go through the BF16X3 code
 
 
@@ -213,6 +215,8 @@ SIGNATURES = {
     'sedt_scaler_update': (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sedt_mel_ok': (_i, [_i, _i, _i, _i]),
     'sedt_mel_spectrogram': (_i, [_vp, _i, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'sedt_resample_ok': (_i, [_i, _i, _i, _i, _i, _i64]),
+    'sedt_resample': (_i, [_vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _i64, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_query_patches': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),

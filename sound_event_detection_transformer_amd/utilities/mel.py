@@ -12,8 +12,9 @@ becomes
     amp, nframes = mel(waves)                      # ONE launch for the batch (sedt_mel_spectrogram); amp stays on the device
     x = DeviceBoxTransform(frames, scaler=scaler)(amp, nframes=nframes)
 
-File decoding, down-mixing and resampling (read_audio, SedData.py:361-377) stay on the host; so does the dB step's other home, the
-compute_log=True branch no driver takes (ApplyLog lives in sedt_box_transform).
+File decoding (read_audio, SedData.py:361-377) stays on the host; read_audio's down-mix and resampling are utilities/resample.py
+(DeviceResampler: its (wave, samples per clip) go as they are into ``mel(wave, lengths=...)``).  The dB step's other home, the
+compute_log=True branch no driver takes, is not built (ApplyLog lives in sedt_box_transform).
 
 ``mel_tables`` is the host half: the window, the FFT twiddles and the filterbank as a band-wise CSR table, all computed in float64 and
 rounded once to f32 - the kernel evaluates no sine and no mel formula.  It needs no GPU."""
@@ -140,7 +141,7 @@ class DeviceMelSpectrogram(object):
         if not clips:
             return torch.empty((0, 1), dtype=torch.float32, device=self.dev), []
         if any(c.ndim != 1 for c in clips):
-            raise ValueError('mono waveforms expected: every clip 1-D (down-mixing stays on the host)')
+            raise ValueError('mono waveforms expected: every clip 1-D (utilities.resample.DeviceResampler down-mixes on the device)')
         pcm = len(clips) > 0 and all(c.dtype == np.int16 for c in clips)
         ns = [int(c.shape[0]) for c in clips]
         B, stride = len(clips), max(ns, default=1)

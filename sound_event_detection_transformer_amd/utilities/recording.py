@@ -150,7 +150,8 @@ class RecordingDetector(object):
     ``batch_windows`` the windows per replay; ``merge_gap`` seconds: events of a class this close are one event; ``cap`` the events
     per (threshold, recording, class) the output holds (default min(4096, windows * Q)).
 
-    A call takes a list of 1-D float32 / int16 waveforms (host or device) and their names and returns ({at_m: RecordingPredictions},
+    A call takes a list of 1-D float32 / int16 waveforms (host or device) at mel.sr - or, with ``sample_rates``, recordings at any rate,
+    mono or interleaved (frames, channels), resampled on the device at ``resample_quality`` - and their names and returns ({at_m: RecordingPredictions},
     WindowTags).  Per batch of windows: one strided copy launch cuts the windows out of the recordings (ops.copy2d: src stride = hop,
     dst stride = window), mel + box transform write the graph's static input, one GraphedDetectStep replay, one more copy2d launch
     per fusion strategy appends the batch's valid rows to the call's record buffer - nothing is read back between batches.  Then one
@@ -158,7 +159,7 @@ class RecordingDetector(object):
     host buffers (``submit`` returns the handle, a call is ``submit(...).result()``)."""
 
     def __init__(self, model, postprocessor, decoder, mel, transform, window_seconds, hop_seconds, batch_windows=8, merge_gap=0.0, cap=None,
-                 at=True, threshold=0.5, graphed=True):
+                 at=True, threshold=0.5, graphed=True, resample_quality='kaiser_best'):
         if float(window_seconds) != decoder.max_len:
             raise ValueError(f'RecordingDetector: window_seconds {window_seconds} is not the decoder\'s max_len_seconds {decoder.max_len}: '
                              'the events of a window are clipped to the window')
@@ -182,6 +183,7 @@ class RecordingDetector(object):
         self.sizes = torch.full((self.B,), self.window_seconds, dtype=torch.float32, device=self.dev)
         self.step = None
         self._up, self._host, self._serial, self._keep = {}, None, 0, None
+        self.resample_quality, self._resamplers = resample_quality, {}
 
     # ------------------------------------------------------------------ pieces
     def plan(self, lengths):
@@ -194,12 +196,47 @@ class RecordingDetector(object):
             check_depth(t[off[r]:off[r + 1]], self.window_seconds, self.merge_gap, f'recording {r}')
         return off, start, t, np.asarray(lengths, np.float64) / float(self.mel.sr)
 
-    def _stage(self, waves):
+    def resampler(self, rate):
+        """the DeviceResampler from ``rate`` to mel.sr, made at first use and kept (its table stays on the device)"""
+        rs = self._resamplers.get(int(rate))
+        if rs is None:
+            from .resample import DeviceResampler
+            rs = self._resamplers[int(rate)] = DeviceResampler(int(rate), self.mel.sr, self.resample_quality, device=self.dev)
+        return rs
+
+    def _stage_resampled(self, waves, sample_rates):
+        """_stage for recordings at their own sample rates, 1-D or interleaved (frames, channels): grouped by rate, every group ONE
+        sedt_resample launch that down-mixes, converts to mel.sr and writes straight into the flat vector at the recordings'
+        offsets (a recording already at mel.sr goes through the identity plan).  Lengths and offsets are the resampled ones."""
+        rates = [int(sample_rates)] * len(waves) if np.ndim(sample_rates) == 0 else [int(r) for r in sample_rates]
+        if len(rates) != len(waves):
+            raise ValueError('sample_rates: one rate, or one per recording')
+        groups = {}
+        for i, r in enumerate(rates):
+            groups.setdefault(r, []).append(i)
+        staged, ns = {}, [0] * len(waves)
+        for r, idx in groups.items():
+            rs = self.resampler(r)
+            clips, pins = rs.stage([waves[i] for i in idx])
+            staged[r] = (rs, clips, pins)
+            for i, (_, n, _) in zip(idx, clips):
+                ns[i] = rs.n_out(n)
+        off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        flat = torch.empty(max(int(off[-1]), 1), dtype=torch.float32, device=self.dev)
+        for r, idx in groups.items():
+            rs, clips, _ = staged[r]
+            rs.launch(clips, flat, [int(off[i]) for i in idx], [ns[i] for i in idx])
+        return flat, off, ns, [(clips, pins) for _, clips, pins in staged.values()]     # the raw input lives as long as the flat vector
+
+    def _stage(self, waves, sample_rates=None):
         """the recordings as ONE float32 device vector (every recording 4-byte aligned by construction) and their sample offsets.
-        Host waveforms go through one pinned buffer; int16 PCM is widened as the mel kernel widens it (x / 32768, exact)."""
+        Host waveforms go through one pinned buffer; int16 PCM is widened as the mel kernel widens it (x / 32768, exact).
+        With ``sample_rates``: _stage_resampled."""
+        if sample_rates is not None:
+            return self._stage_resampled(waves, sample_rates)
         ns = [int(w.shape[0]) for w in waves]
         if any(getattr(w, 'ndim', 1) != 1 for w in waves):
-            raise ValueError('mono waveforms expected: every recording 1-D (down-mixing stays on the host)')
+            raise ValueError('mono waveforms expected: every recording 1-D (pass sample_rates= to down-mix and resample on the device)')
         off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
         flat = torch.empty(max(int(off[-1]), 1), dtype=torch.float32, device=self.dev)
         host = None
@@ -259,10 +296,10 @@ class RecordingDetector(object):
         return raw[:host.nbytes].view({np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64}[host.dtype])
 
     # ------------------------------------------------------------------ the call
-    def records(self, waves):
+    def records(self, waves, sample_rates=None):
         """windows -> the per-window event records: ({at_m: int32 [K, W, 1 + 5 Q] on the device}, tags (W, C) int64 on the device or
-        None, plan) - what ``stitch`` takes"""
-        flat, rec_off, ns, _host = self._stage(waves)
+        None, plan) - what ``stitch`` takes.  sample_rates: see submit()"""
+        flat, rec_off, ns, _host = self._stage(waves, sample_rates)
         plan = self.plan(ns)
         win_off, start, _, _ = plan
         W, K, fusion = len(start), self.decoder.K, self.decoder.fusion
@@ -306,15 +343,18 @@ class RecordingDetector(object):
         res = {m: ops.stitch_events(rec[m], d_off, d_t, d_dur, self.decoder.C, self.merge_gap, cap, n_windows=W) for m in rec}
         return res, cap
 
-    def submit(self, waves, filenames):
+    def submit(self, waves, filenames, sample_rates=None):
         """everything of a call enqueued on the current stream, the copies of counts, lists, status and tags into the next slot of a ring
         of pinned host buffers included (as EventDecoder.fetch: a slot is reused only after its copies have finished).  Returns the
         handle whose ``result()`` waits for them: submit the next call before asking for this one's result and the host formatting
-        runs beside the device."""
+        runs beside the device.  ``sample_rates`` (one int, or one per recording): the recordings are at these rates and may be
+        interleaved (frames, channels); they are down-mixed and resampled to mel.sr on the device (utilities/resample.py, one launch
+        per distinct rate), and window plan, durations and event times follow from the resampled lengths.  None: the recordings
+        are mono and at mel.sr already."""
         waves, filenames = list(waves), list(filenames)
         if len(waves) != len(filenames) or not waves:
             raise ValueError('RecordingDetector: one name per recording, at least one recording')
-        rec, tags, plan = self.records(waves)
+        rec, tags, plan = self.records(waves, sample_rates)
         res, cap = self.stitch(rec, plan)
         key = (len(filenames), len(plan[1]), cap, tags is not None)
         ring = self._host if self._host is not None and self._host['key'] == key else None
@@ -339,8 +379,8 @@ class RecordingDetector(object):
         keep, self._keep = self._keep, None             # the staged recordings live until the copies behind them have run
         return PendingDetection(self, ring, k, self._serial, plan, filenames, cap, keep)
 
-    def __call__(self, waves, filenames):
-        return self.submit(waves, filenames).result()
+    def __call__(self, waves, filenames, sample_rates=None):
+        return self.submit(waves, filenames, sample_rates).result()
 
 
 class PendingDetection(object):
