@@ -41,6 +41,8 @@
  *                                                                             utilities/metrics.py:120-145, 325-330 (psds_eval)
  *   sedt_stitch_events                                                        no counterpart (the reference scores 10 s clips only):
  *                                                                             the windows' event records -> one list per recording
+ *   sedt_recording_event_counts / sedt_recording_segment_counts               no counterpart: those lists against a recording's annotations,
+ *                                                                             sed_eval's event- and segment-based counts at every threshold
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -913,6 +915,56 @@ int sedt_psds_update(const int32_t* records, const int32_t* clip_idx, const int3
 int sedt_stitch_events(const int32_t* records, const int32_t* win_off, const double* win_start, const double* rec_dur, int K, int W,
                        int W_stride, int R, int Q, int C, double merge_gap, int cap, int32_t* count, int32_t* out, int32_t* status,
                        void* stream);
+
+/* sedt_recording_event_counts / sedt_recording_segment_counts (no counterpart in the reference, which scores 10 s dataset clips only;
+ * DESIGN.md section 4, "Scoring recordings", holds the definition and tests/recording_metrics_ref.py restates it): the stitched event
+ * lists of sedt_stitch_events scored against the recordings' annotations where they lie - lists in, counts out.
+ * Scope: per fusion strategy, threshold k, recording r, class c.  Float64, plain subtract / multiply / divide / compare, no contraction.
+ *   estimates   the first count[k][r][c] slots of the stitch output out[k][r][c] (onset = the f64 in words 0-1, offset = the f64 in
+ *               words 2-3), as stitch wrote them: no second clip, no duration filter; ascending by onset and disjoint.
+ *   references  the recording's annotated events of class c, sorted by the host by (onset, offset, input order); any number of them,
+ *               and those of one class may overlap.  CSR over (reference recording, class): the events of class c of reference
+ *               recording i are ref_on / ref_end [ref_off[i * C + c] .. ref_off[i * C + c + 1]); ref_off [n_ref_rec * C + 1] int32,
+ *               n_ref_events the length of ref_on / ref_end (offsets are clamped to it).
+ *   evaluated   only recordings with an entry in the reference: rec_idx[r] = -1 (or outside 0 .. n_ref_rec - 1) adds nothing anywhere -
+ *               deliberately simpler than the clip-level outer merge of sedt_event_metrics_update.  A recording annotated with an
+ *               empty list is evaluated: its estimates count as n_sys, as false positives and as I.
+ *   event-based a hit is |on_r - on_e| <= t_collar and |off_r - off_e| <= max(t_collar, pct * (off_r - on_r)), sed_eval's test as
+ *               event_hit_graph writes it; tp = the size of a maximum-cardinality matching of the hit graph of class c over the WHOLE
+ *               recording, or (optimal == 0) of sed_eval's greedy pass: references in table order, each takes the first estimate
+ *               in onset order that is still free and that it hits.
+ *   no limit    a hit needs onsets within t_collar, so the two lists are merged by onset (at equal onsets the estimate first) and a
+ *               BLOCK is closed between two consecutive items a <= b of the merged order with fl(b - a) > t_collar.  No hit
+ *               crosses such a cut: for p <= a < b <= q the real difference q - p >= b - a, rounding is monotone, so fl(q - p) >=
+ *               fl(b - a) > t_collar.  The matching (maximum, or greedy in the orders above) is the sum over the blocks.  Blocks
+ *               are formed while both lists have items left: what remains of one list behind the last block matches nothing and is
+ *               not walked.  A block holds at most 64 references and 64 estimates; a denser one raises status 2, it is never
+ *               silently mis-counted.
+ *   presence    per class "count[k][r][c] > 0" against "class c has a reference event in r": tag_counts {tp, fp, fn}.
+ *   segments    (sedt_recording_segment_counts) at time_resolution rho an event makes its class active in the segments floor(on / rho)
+ *               <= s < ceil(off / rho), both quotients float64 divisions; events of a class OR together, an empty range sets
+ *               nothing.  Class-wise seg_counts {tp, n_ref, n_sys}; per segment over the classes S += min(Nref, Nsys) - Ntp,
+ *               D += max(0, Nref - Nsys), I += max(0, Nsys - Nref).  The recording spans n_words[r] words of 64 segments (int32 [R];
+ *               the host passes ceil(ceil(max(rec_dur[r], largest reference offset) / rho) / 64)); segments past them are not
+ *               counted.  No limit on the number of segments: the sweep holds two 64-segment words per class.
+ * Inputs: sedt_stitch_events' count [K][R][C], out [K][R][C][cap][8 words] (8-byte aligned), status [K][R] (`stitch_status`) and cap;
+ * rec_idx [R] int32: the recording's index in the reference table.
+ * Counters (int64, integer atomics only, so the sums do not depend on launch order; zero them per evaluation), row `fusion` of
+ *   ev_counts [n_fusion][K][C][3], tag_counts [n_fusion][K][C][3], seg_counts [n_fusion][K][C][3], sdi_counts [n_fusion][K][3].
+ * status [K][R] int32, written by every launch: 0; 1 the stitch status of (k, r) is non-zero or some count[k][r][c] > cap (the lists
+ *   are not complete); 4 a list (estimates or references) is not ascending by onset or holds a non-finite time; 2 a block over
+ *   capacity (event counts only) - in this order of precedence.  With a status raised the counters may hold partial sums of that
+ *   recording.  count is clamped to 0 .. cap before it indexes anything: nothing is read or written out of bounds in any case.
+ * 1 <= C <= 63, 1 <= K <= 1024, R >= 0 (R == 0 launches nothing), cap >= 1; t_collar finite and >= 0; time_resolution finite and > 0.
+ * Events per list and segments per recording are bounded by int32 indexing only. */
+int sedt_recording_event_counts(const int32_t* count, const int32_t* out, const int32_t* stitch_status, const int32_t* rec_idx,
+                                const int32_t* ref_off, const double* ref_on, const double* ref_end, int n_ref_rec, int n_ref_events,
+                                int K, int R, int C, int cap, int n_fusion, int fusion, double t_collar, double pct, int optimal,
+                                int64_t* ev_counts, int64_t* tag_counts, int32_t* status, void* stream);
+int sedt_recording_segment_counts(const int32_t* count, const int32_t* out, const int32_t* stitch_status, const int32_t* rec_idx,
+                                  const int32_t* ref_off, const double* ref_on, const double* ref_end, const int32_t* n_words,
+                                  int n_ref_rec, int n_ref_events, int K, int R, int C, int cap, int n_fusion, int fusion,
+                                  double time_resolution, int64_t* seg_counts, int64_t* sdi_counts, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ input side on the device (utilities/BoxTransforms.py,
  * utilities/mixup.py)

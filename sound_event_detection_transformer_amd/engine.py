@@ -949,6 +949,19 @@ def detect_recordings(model, postprocessor, decoder, mel, transform, waves, file
     return det(waves, filenames, sample_rates)
 
 
+def evaluate_recordings(detector, metrics, calls):
+    """annotated recordings of any length scored without leaving the device: ``detector`` a utilities.recording.RecordingDetector,
+    ``metrics`` a utilities.recording_metrics.RecordingMetrics bound to the detector's decoder, its reference set, ``calls`` an
+    iterable of (waves, filenames[, sample_rates]) - one detector call each.  The counters are reset, every call is submitted with
+    ``metrics=`` (its stitched lists are counted right behind the stitch launches; the call's predictions are not formatted), and
+    the scores are read back once: returns ``metrics.compute()``, {at_m: [per threshold of the decoder's grid what
+    utilities.metrics.finalize returns]}.  ``metrics.class_wise_thresholds(at_m)`` then picks one threshold per class."""
+    metrics.reset()
+    for call in calls:
+        detector.submit(call[0], call[1], call[2] if len(call) > 2 else None, metrics=metrics)
+    return metrics.compute()
+
+
 def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, threshold=0.5, graphed=True, max_targets=32):
     """engine.evaluate (engine.py:199-216) without leaving the device: ``batches`` yields (input, targets, clip indices into the
     metrics' reference) - the reference's data_prefetcher gives ((input, targets), indexes).  The counters are reset, every batch

@@ -231,6 +231,8 @@ SIGNATURES = {
     'sedt_event_sweep_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),
     'sedt_psds_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp]),
     'sedt_stitch_events': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    'sedt_recording_event_counts': (_i, [_vp] * 7 + [_i] * 8 + [_d, _d, _i, _vp, _vp, _vp, _vp]),
+    'sedt_recording_segment_counts': (_i, [_vp] * 8 + [_i] * 8 + [_d, _vp, _vp, _vp, _vp]),
     'sedt_hungarian_batch': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'sedt_adamw_clip': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _i, _vp]),
 }

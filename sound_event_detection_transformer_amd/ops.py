@@ -2004,6 +2004,61 @@ def stitch_events(records, win_off, win_start, rec_dur, n_classes, merge_gap=0.0
     return count, out, status
 
 
+def _recording_args(count, out, stitch_status, cap, rec_idx, table, counters, status):
+    """the shape, dtype and contiguity asserts the two recording-metrics launches share; returns (K, R, C, n_fusion, status)"""
+    _dev_check(count, out, stitch_status, rec_idx, table['off'], table['on'], table['end'], status, *counters)
+    K, R, C = count.shape
+    assert count.dtype == torch.int32 and count.dim() == 3 and count.is_contiguous()
+    assert out.dtype == torch.int32 and tuple(out.shape) == (K, R, C, int(cap), STITCH_WORDS) and out.is_contiguous()
+    assert stitch_status.dtype == torch.int32 and tuple(stitch_status.shape) == (K, R) and stitch_status.is_contiguous()
+    assert rec_idx.dtype == torch.int32 and rec_idx.numel() == R and rec_idx.is_contiguous()
+    n_rec, n_ev = int(table['n_rec']), int(table['n_events'])
+    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_rec * C + 1 and table['off'].is_contiguous()
+    assert table['on'].dtype == torch.float64 and table['on'].numel() >= n_ev and table['on'].is_contiguous()
+    assert table['end'].dtype == torch.float64 and table['end'].numel() >= n_ev and table['end'].is_contiguous()
+    nf = counters[0].shape[0]
+    if status is None:
+        status = torch.empty((K, R), device=count.device, dtype=torch.int32)
+    assert status.dtype == torch.int32 and tuple(status.shape) == (K, R) and status.is_contiguous()
+    return K, R, C, nf, status
+
+
+def recording_event_counts(count, out, stitch_status, cap, rec_idx, table, ev_counts, tag_counts, fusion, t_collar=0.2, pct=0.2,
+                           optimal=True, status=None):
+    """sed_eval's event-based counts and the recording-level presence counts of one fusion strategy's stitched event lists
+    (stitch_events' count [K,R,C], out [K,R,C,cap,8], status [K,R] and cap) against the recordings' annotations, accumulated into
+    ev_counts / tag_counts int64 [n_fusion, K, C, 3] at row ``fusion`` (include/sedt_hip.h: sedt_recording_event_counts).
+    rec_idx int32 [R]: the recordings' indices in the reference table (-1 = not evaluated); table: dict of the device CSR table over
+    (reference recording, class) - off int32 [n_rec * C + 1], on / end float64 [n_events] - with the host ints n_rec and n_events.
+    Returns status int32 [K, R] (``status`` when given).  Nothing is read back."""
+    K, R, C, nf, status = _recording_args(count, out, stitch_status, cap, rec_idx, table, (ev_counts, tag_counts), status)
+    assert ev_counts.dtype == torch.int64 and tuple(ev_counts.shape) == (nf, K, C, 3) and ev_counts.is_contiguous()
+    assert tag_counts.dtype == torch.int64 and tuple(tag_counts.shape) == (nf, K, C, 3) and tag_counts.is_contiguous()
+    L.check(L.load().sedt_recording_event_counts(_p(count), _p(out), _p(stitch_status), _p(rec_idx), _p(table['off']), _p(table['on']),
+                                                 _p(table['end']), int(table['n_rec']), int(table['n_events']), K, R, C, int(cap), nf,
+                                                 int(fusion), float(t_collar), float(pct), int(bool(optimal)), _p(ev_counts),
+                                                 _p(tag_counts), _p(status), L.stream_ptr()), 'recording_event_counts')
+    return status
+
+
+def recording_segment_counts(count, out, stitch_status, cap, rec_idx, table, n_words, seg_counts, sdi_counts, fusion, time_resolution=1.0,
+                             status=None):
+    """sed_eval's segment-based counts of one fusion strategy's stitched event lists against the recordings' annotations at
+    ``time_resolution`` seconds per segment, accumulated into seg_counts int64 [n_fusion, K, C, 3] and sdi_counts int64 [n_fusion, K, 3]
+    at row ``fusion`` (include/sedt_hip.h: sedt_recording_segment_counts).  n_words int32 [R]: the 64-segment words every recording
+    spans; the other arguments as recording_event_counts.  Returns status int32 [K, R].  Nothing is read back."""
+    K, R, C, nf, status = _recording_args(count, out, stitch_status, cap, rec_idx, table, (seg_counts, sdi_counts), status)
+    _dev_check(n_words)
+    assert n_words.dtype == torch.int32 and n_words.numel() == R and n_words.is_contiguous()
+    assert seg_counts.dtype == torch.int64 and tuple(seg_counts.shape) == (nf, K, C, 3) and seg_counts.is_contiguous()
+    assert sdi_counts.dtype == torch.int64 and tuple(sdi_counts.shape) == (nf, K, 3) and sdi_counts.is_contiguous()
+    L.check(L.load().sedt_recording_segment_counts(_p(count), _p(out), _p(stitch_status), _p(rec_idx), _p(table['off']), _p(table['on']),
+                                                   _p(table['end']), _p(n_words), int(table['n_rec']), int(table['n_events']), K, R, C,
+                                                   int(cap), nf, int(fusion), float(time_resolution), _p(seg_counts), _p(sdi_counts),
+                                                   _p(status), L.stream_ptr()), 'recording_segment_counts')
+    return status
+
+
 def mixup(x1, x2, jobs, out=None):
     """feature half of utilities/mixup.py: out[i] = lam * x1[src1] + (1 - lam) * x2[src2] / x1[src1] / x2[src2] per job record
     (jobs: uint8 device tensor of n 16-byte records {int32 src1, src2, mode; f32 lam}); x1 / x2 / out f32 [*, clip...]"""

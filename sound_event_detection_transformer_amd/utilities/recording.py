@@ -343,19 +343,23 @@ class RecordingDetector(object):
         res = {m: ops.stitch_events(rec[m], d_off, d_t, d_dur, self.decoder.C, self.merge_gap, cap, n_windows=W) for m in rec}
         return res, cap
 
-    def submit(self, waves, filenames, sample_rates=None):
+    def submit(self, waves, filenames, sample_rates=None, metrics=None):
         """everything of a call enqueued on the current stream, the copies of counts, lists, status and tags into the next slot of a ring
         of pinned host buffers included (as EventDecoder.fetch: a slot is reused only after its copies have finished).  Returns the
         handle whose ``result()`` waits for them: submit the next call before asking for this one's result and the host formatting
         runs beside the device.  ``sample_rates`` (one int, or one per recording): the recordings are at these rates and may be
         interleaved (frames, channels); they are down-mixed and resampled to mel.sr on the device (utilities/resample.py, one launch
         per distinct rate), and window plan, durations and event times follow from the resampled lengths.  None: the recordings
-        are mono and at mel.sr already."""
+        are mono and at mel.sr already.  ``metrics`` (a utilities.recording_metrics.RecordingMetrics with its reference set): the
+        stitched lists are scored against the annotations where they lie - ``metrics.update`` is enqueued right after the stitch
+        launches, on the same stream, and reads nothing back."""
         waves, filenames = list(waves), list(filenames)
         if len(waves) != len(filenames) or not waves:
             raise ValueError('RecordingDetector: one name per recording, at least one recording')
         rec, tags, plan = self.records(waves, sample_rates)
         res, cap = self.stitch(rec, plan)
+        if metrics is not None:
+            metrics.update(res, cap, filenames, durations=plan[3])
         key = (len(filenames), len(plan[1]), cap, tags is not None)
         ring = self._host if self._host is not None and self._host['key'] == key else None
         if ring is None:                                # another shape: a new ring (a handle still out keeps its own alive)
@@ -379,8 +383,8 @@ class RecordingDetector(object):
         keep, self._keep = self._keep, None             # the staged recordings live until the copies behind them have run
         return PendingDetection(self, ring, k, self._serial, plan, filenames, cap, keep)
 
-    def __call__(self, waves, filenames, sample_rates=None):
-        return self.submit(waves, filenames, sample_rates).result()
+    def __call__(self, waves, filenames, sample_rates=None, metrics=None):
+        return self.submit(waves, filenames, sample_rates, metrics).result()
 
 
 class PendingDetection(object):

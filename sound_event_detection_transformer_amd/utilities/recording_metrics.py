@@ -1,0 +1,254 @@
+"""Recordings of any length scored against their annotations, on the device.  ``utilities.recording.RecordingDetector`` leaves one
+stitched event list per (threshold, recording, class) on the device; ``RecordingMetrics`` is one more consumer of those lists: lists
+in, counts out (ops.recording_event_counts / ops.recording_segment_counts, csrc/recmetrics.hip), at every threshold of the decoder's
+grid, without per-clip records, without a criterion and without the per-clip limits of EventMetrics (64 reference events, 1024
+segments).  DESIGN.md section 4 ("Scoring recordings") holds the definition:
+
+Scope: per fusion strategy, threshold k, recording r, class c.  Float64, plain subtract / multiply / divide / compare.
+  * estimates: the first count[k][r][c] slots of the stitch output, as stitch wrote them (no second clip, no duration filter),
+    ascending by onset and disjoint.  References: the recording's annotated events of class c, sorted here by (onset, offset, input
+    order); any number of them, and those of one class may overlap.
+  * evaluated recordings: only those with an entry in the reference; a filename that is absent adds nothing anywhere (deliberately
+    simpler than the clip-level outer merge of EventMetrics).  A recording annotated with an empty list is evaluated: its estimates
+    count as n_sys, as false positives and as I.
+  * event-based {tp, n_ref, n_sys}: sed_eval's hit test (|on_r - on_e| <= t_collar, |off_r - off_e| <= max(t_collar, pct * (off_r -
+    on_r))); tp = the size of a maximum-cardinality matching of the hit graph of class c over the WHOLE recording; ``optimal=False``
+    selects sed_eval's greedy pass (references in table order, each takes the first estimate in onset order still free that it
+    hits).  No limit on events: the two lists are merged by onset and cut into blocks wherever two consecutive onsets differ by more
+    than t_collar (no hit crosses such a cut, so the matching is the sum over the blocks); a block of more than 64 references or 64
+    estimates raises a status, it is never silently mis-counted.
+  * recording-level presence {tp, fp, fn} per class: "count[k][r][c] > 0" against "class c has a reference event in r".
+  * with ``time_resolution`` = rho, segment-based {tp, n_ref, n_sys} and {S, D, I} as EventMetrics documents them (an event is active
+    in floor(on / rho) <= s < ceil(off / rho), float64 divisions), over ceil(max(recording duration, largest reference offset) /
+    rho) segments - any number of them.  Negative reference times are refused.
+  * status per (threshold, recording) and launch: 1 the lists are not complete (a stitch status, or more events than ``cap``), 4 a list
+    is not ascending by onset or holds a non-finite time, 2 a block over capacity.  ``compute()`` raises and names the recording,
+    the threshold and the reason.
+
+    metrics = RecordingMetrics(decoder, time_resolution=1.0).set_reference({'street.wav': [('Speech', 1.5, 4.25), ...]})
+    scores = engine.evaluate_recordings(detector, metrics, [([wave], ['street.wav'])])      # {at_m: [per threshold: finalize's dict]}
+    best = metrics.class_wise_thresholds(1)                                                  # one threshold per class, no criterion
+
+``reference_table``, ``finish`` and ``status_error`` are the host half and need no GPU."""
+import math
+
+import numpy as np
+import torch
+
+from .. import ops
+from .metrics import finalize
+from .operating_points import select_class_wise
+from .predictions import operating_point
+from .transforms import PinnedRing
+
+MAX_WORDS = (1 << 25) - 1          # 64-segment words of one recording (csrc/recmetrics.hip: SEDT_RM_MAXWORDS)
+STATUS_REASONS = {1: 'its stitched lists are not complete (a stitch status was raised, or a class holds more events than cap)',
+                  2: 'more than 64 reference events or 64 estimates of one class lie in one block of onsets chained within t_collar',
+                  4: 'an event list is not ascending by onset or holds a non-finite time'}
+
+
+def reference_table(reference, labels, segments=False):
+    """{filename: [(label, onset, offset), ...]} -> the CSR table over (reference recording, class) the kernels read, as host arrays:
+    {'names' (the filenames in the dict's order), 'index' {filename: i}, 'off' int32 [N * C + 1], 'on' / 'end' float64 [E] (per
+    (recording, class) sorted by (onset, offset, input order)), 'max_end' float64 [N] (0 for an empty list)}.  label: a class name or
+    index.  Unknown labels and non-finite times are refused, with ``segments`` negative times too."""
+    labels = list(labels)
+    index, C = {l: i for i, l in enumerate(labels)}, len(labels)
+    names, off, on, end, max_end = [], [0], [], [], []
+    for name, events in reference.items():
+        per = [[] for _ in range(C)]
+        for n, (label, onset, offset) in enumerate(events):
+            if label in index:
+                c = index[label]
+            elif isinstance(label, (int, np.integer)) and 0 <= int(label) < C:
+                c = int(label)
+            else:
+                raise ValueError(f'set_reference: recording {name!r}: class {label!r} is not one of the {C} labels')
+            onset, offset = float(onset), float(offset)
+            if not (math.isfinite(onset) and math.isfinite(offset)):
+                raise ValueError(f'set_reference: recording {name!r}: non-finite event time ({onset}, {offset})')
+            if segments and (onset < 0 or offset < 0):
+                raise ValueError(f'set_reference: recording {name!r}: negative event time ({onset}, {offset}) in a segment-based '
+                                 'evaluation')
+            per[c].append((onset, offset, n))
+        for c in range(C):
+            per[c].sort()
+            on += [e[0] for e in per[c]]
+            end += [e[1] for e in per[c]]
+            off.append(len(on))
+        names.append(name)
+        max_end.append(max([e[1] for p in per for e in p], default=0.0))
+    if len(on) > 2 ** 31 - 1:
+        raise ValueError(f'set_reference: {len(on)} reference events exceed int32 indexing')
+    return {'names': names, 'index': {n: i for i, n in enumerate(names)}, 'off': np.asarray(off, np.int32),
+            'on': np.asarray(on, np.float64), 'end': np.asarray(end, np.float64), 'max_end': np.asarray(max_end, np.float64)}
+
+
+def segment_words(rec_dur, max_end, time_resolution):
+    """the 64-segment words a recording spans: ceil(ceil(max(rec_dur, largest reference offset) / rho) / 64) (float64 division)"""
+    n = math.ceil(max(float(rec_dur), float(max_end), 0.0) / float(time_resolution))
+    words = -(-n // 64)
+    if words > MAX_WORDS:
+        raise ValueError(f'{max(float(rec_dur), float(max_end))} s at time_resolution {time_resolution} s are {n} segments: more than '
+                         f'int32 indexing holds ({MAX_WORDS * 64})')
+    return words
+
+
+def status_error(status, filenames, thresholds, what):
+    """None, or the RuntimeError for the first non-zero entry of a launch's status [K, R]"""
+    bad = np.argwhere(np.asarray(status) != 0)
+    if not len(bad):
+        return None
+    k, r = (int(v) for v in bad[0])
+    s = int(status[k][r])
+    return RuntimeError(f'{what}: recording {filenames[r]!r} at threshold {thresholds[k]}: status {s} ({STATUS_REASONS.get(s, "unknown")})')
+
+
+def finish(ev, tag, labels, fusion, seg=None, sdi=None):
+    """counter arrays ev / tag [n_fusion, K, C, 3] (and seg [n_fusion, K, C, 3], sdi [n_fusion, K, 3]) -> {at_m: [per threshold what
+    utilities.metrics.finalize returns for that threshold's slices]}: the recording-level presence scores under its 'clip' key"""
+    K = ev.shape[1]
+    per_k = [finalize(ev[:, k], tag[:, k], labels, fusion, at_counted=False,
+                      **({} if seg is None else dict(seg=seg[:, k], sdi=sdi[:, k]))) for k in range(K)]
+    return {m: [per_k[k][m] for k in range(K)] for m in fusion}
+
+
+class RecordingMetrics(object):
+    """event-based, recording-level and (with ``time_resolution``) segment-based counts of a RecordingDetector's stitched lists against
+    annotations, at every threshold of ``event_decoder`` (a utilities.predictions.EventDecoder: its labels, its K thresholds, its
+    fusion strategies).  int64 counters on the device: ev / tag [n_fusion, K, C, 3], seg [n_fusion, K, C, 3], sdi [n_fusion, K, 3].
+    See the module docstring."""
+
+    def __init__(self, event_decoder, t_collar=0.2, percentage_of_length=0.2, optimal=True, time_resolution=None, device=None):
+        self.decoder = event_decoder
+        self.labels, self.C, self.K, self.fusion = list(event_decoder.labels), event_decoder.C, event_decoder.K, tuple(event_decoder.fusion)
+        self.device = event_decoder.device if device is None else torch.device(device)
+        self.t_collar, self.pct, self.optimal = float(t_collar), float(percentage_of_length), bool(optimal)
+        if not (0.0 <= self.t_collar < float('inf')) or math.isnan(self.pct):
+            raise ValueError(f'RecordingMetrics: t_collar {t_collar!r} is not a finite number >= 0 (or percentage_of_length is NaN)')
+        self.time_resolution = None if time_resolution is None else float(time_resolution)
+        if self.time_resolution is not None and not (math.isfinite(self.time_resolution) and self.time_resolution > 0):
+            raise ValueError(f'RecordingMetrics: time_resolution {time_resolution!r} is not a positive number of seconds')
+        shape = (len(self.fusion), self.K, self.C, 3)
+        self.ev = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        self.tag = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        self.seg = self.sdi = None
+        if self.time_resolution is not None:
+            self.seg = torch.zeros(shape, dtype=torch.int64, device=self.device)
+            self.sdi = torch.zeros((len(self.fusion), self.K, 3), dtype=torch.int64, device=self.device)
+        self.host, self.table = None, None
+        self._status, self._up = [], {}
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def set_reference(self, reference):
+        """reference: {filename: [(label, onset, offset), ...]} - label a class name or index, times in seconds from the start of the
+        recording; a filename that is absent is not evaluated, one with an empty list is.  Sorts, builds the CSR table and uploads it
+        once; the counters are not touched."""
+        self.host = reference_table(reference, self.labels, segments=self.time_resolution is not None)
+        h = self.host
+        pad = lambda a: a if a.size else np.zeros(1, a.dtype)
+        self.table = {'off': torch.from_numpy(h['off']).to(self.device), 'on': torch.from_numpy(pad(h['on'])).to(self.device),
+                      'end': torch.from_numpy(pad(h['end'])).to(self.device), 'n_rec': len(h['names']), 'n_events': int(h['on'].size)}
+        return self
+
+    def recording_index(self, filenames):
+        """the recordings' indices in the reference table as host int32 [R] (-1: not in the reference, not evaluated)"""
+        return np.asarray([self.host['index'].get(f, -1) for f in filenames], np.int32)
+
+    def _upload(self, name, host):
+        ring = self._up.get(name)
+        if ring is None:
+            ring = self._up[name] = PinnedRing(self.device)
+        host = np.ascontiguousarray(host, np.int32)
+        return ring.upload(host.view(np.uint8).reshape(-1))[:host.nbytes].view(torch.int32)
+
+    def counters(self):
+        """every device counter tensor: [ev, tag] (+ [seg, sdi] with segment-based scores)"""
+        return [t for t in (self.ev, self.tag, self.seg, self.sdi) if t is not None]
+
+    def reset(self):
+        """zero the counters and forget the statuses (start of an evaluation)"""
+        for t in self.counters():
+            t.zero_()
+        self._status = []
+        return self
+
+    def update(self, stitched, cap, filenames, durations=None):
+        """one detector call: ``stitched`` {at_m: (count, out, status)} and ``cap`` as ``RecordingDetector.stitch`` returns them,
+        ``filenames`` the recordings' names, ``durations`` their lengths in seconds (needed with ``time_resolution``: the plan's
+        rec_dur).  One launch per fusion strategy, one more each with segments, on the current stream; nothing is read back - the
+        small status tensors stay on the device until compute()."""
+        if self.table is None:
+            raise RuntimeError('RecordingMetrics.update: set_reference() first')
+        filenames = list(filenames)
+        idx = self.recording_index(filenames)
+        words = None
+        if self.seg is not None:
+            if durations is None or len(durations) != len(filenames):
+                raise ValueError('RecordingMetrics.update: segment-based counts need the recordings\' durations, one per recording')
+            words = [segment_words(d, self.host['max_end'][i] if i >= 0 else 0.0, self.time_resolution) for d, i in zip(durations, idx)]
+        for m in self.fusion:
+            count = stitched[m][0]
+            if tuple(count.shape) != (self.K, len(filenames), self.C):
+                raise ValueError(f'RecordingMetrics.update: counts {tuple(count.shape)} for {self.K} thresholds x {len(filenames)} '
+                                 f'recordings x {self.C} classes')
+        if not filenames:
+            return
+        d_idx = self._upload('idx', idx)
+        d_words = None if words is None else self._upload('words', words)
+        thresholds = [operating_point(t) for t in self.decoder.threshold_values]
+        for i, m in enumerate(self.fusion):
+            count, out, st = stitched[m]
+            s = ops.recording_event_counts(count, out, st, cap, d_idx, self.table, self.ev, self.tag, i, t_collar=self.t_collar,
+                                           pct=self.pct, optimal=self.optimal)
+            self._status.append((s, filenames, thresholds, f'recording_event_counts (fusion {m})'))
+            if self.seg is not None:
+                s = ops.recording_segment_counts(count, out, st, cap, d_idx, self.table, d_words, self.seg, self.sdi, i,
+                                                 time_resolution=self.time_resolution)
+                self._status.append((s, filenames, thresholds, f'recording_segment_counts (fusion {m})'))
+
+    def _read(self):
+        """counters (in the order of counters()) and statuses as numpy, from ONE device->host copy"""
+        ts = self.counters() + [s[0].to(torch.int64) for s in self._status]
+        h = torch.cat([t.reshape(-1) for t in ts]).cpu().numpy()
+        got, o = [], 0
+        for t in ts:
+            got.append(h[o:o + t.numel()].reshape(t.shape))
+            o += t.numel()
+        n = len(self.counters())
+        return got[:n], got[n:]
+
+    def _checked(self):
+        counters, statuses = self._read()
+        for st, (_, filenames, thresholds, what) in zip(statuses, self._status):
+            err = status_error(st, filenames, thresholds, what)
+            if err is not None:
+                raise err
+        return counters
+
+    def counts(self):
+        """(ev [n_fusion, K, C, 3] {tp, n_ref, n_sys}, tag [n_fusion, K, C, 3] {tp, fp, fn}) as numpy int64; one device->host copy;
+        raises on a status"""
+        got = self._checked()
+        return got[0], got[1]
+
+    def segment_counts(self):
+        """(seg [n_fusion, K, C, 3] {tp, n_ref, n_sys}, sdi [n_fusion, K, 3] {S, D, I}) as numpy int64, None without time_resolution"""
+        if self.seg is None:
+            return None
+        got = self._checked()
+        return got[2], got[3]
+
+    def compute(self):
+        """{at_m: [per threshold {'f1', 'precision', 'recall', 'class_wise', 'clip': {...}[, 'segment': {...}]}]}: what
+        utilities.metrics.finalize returns for every threshold's slices of the counters, the recording-level presence scores under
+        'clip'.  One device->host copy of counters and statuses; raises on a status, naming recording, threshold and reason."""
+        got = self._checked()
+        seg = {} if self.seg is None else dict(seg=got[2], sdi=got[3])
+        return finish(got[0], got[1], self.labels, self.fusion, **seg)
+
+    def class_wise_thresholds(self, m, default=0.5):
+        """operating_points.select_class_wise on fusion strategy ``m``'s event-based counts and the decoder's grid: one threshold per
+        class tuned on recordings, without a criterion"""
+        ev = self.counts()[0][self.fusion.index(m)]
+        return select_class_wise(ev, self.decoder.threshold_values.copy(), default)
