@@ -43,6 +43,7 @@
  *                                                                             the windows' event records -> one list per recording
  *   sedt_recording_event_counts / sedt_recording_segment_counts               no counterpart: those lists against a recording's annotations,
  *                                                                             sed_eval's event- and segment-based counts at every threshold
+ *   sedt_recording_psds_counts                                                no counterpart: PSDS confusion counts from those lists
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -965,6 +966,45 @@ int sedt_recording_segment_counts(const int32_t* count, const int32_t* out, cons
                                   const int32_t* ref_off, const double* ref_on, const double* ref_end, const int32_t* n_words,
                                   int n_ref_rec, int n_ref_events, int K, int R, int C, int cap, int n_fusion, int fusion,
                                   double time_resolution, int64_t* seg_counts, int64_t* sdi_counts, int32_t* status, void* stream);
+
+/* sedt_recording_psds_counts (no counterpart in the reference, which scores 10 s dataset clips only; DESIGN.md section 4, "PSDS on
+ * recordings", holds the definition and tests/recording_psds_ref.py restates it): the PSDS confusion counts of sedt_psds_update for
+ * the stitched event lists of sedt_stitch_events against the recordings' annotations - lists in, counts out, no limit on the events
+ * of a list.  One wave per (recording, class, threshold).
+ * Inputs: those of sedt_recording_event_counts (count, out, stitch_status, cap, rec_idx and the CSR table ref_off / ref_on / ref_end
+ * with n_ref_rec and n_ref_events), plus ref_pmax [n_ref_events] float64: per (recording, class) list the running maximum of ref_end
+ * (ref_pmax[j] = max of ref_end over the list's events up to and including j), and rec_dur [R] float64: the recordings' lengths in
+ * seconds.
+ * Definition.  Scope: per fusion strategy, threshold k, recording r with rec_idx[r] inside the table; rec_idx[r] of -1 or out of
+ * range adds nothing.  Float64 with no contraction: plain subtract, divide, compare, comparisons >=.  inter(d, g) = min(off_d, off_g) -
+ * max(on_d, on_g) counts only where it is > 0; every term is one division added to a running sum.
+ *   detections  of class c: the first min(count, cap) slots of out[k][r][c], as stitch wrote them (ascending by onset, disjoint).  A
+ *               detection whose off - on is not > 0 takes part in nothing.
+ *   references  of class c': the table's list of (rec_idx[r], c'), in table order.  One whose end - on is not > 0 takes part in nothing.
+ *   DTC   p_d = sum of inter(d, g) / dur_d over the references g of d's class, in table order;  d passes when p_d >= dtc;
+ *   GTC   v_g = sum of inter(d, g) / dur_g over the detections of g's class that passed, in onset order;  v_g >= gtc:
+ *         counts[c][c] += 1;
+ *   CTTC  for every d that failed the DTC and each other class c': sum of inter(d, g) / dur_d over the references of class c' >= cttc:
+ *         counts[class(d)][c'] += 1;  independently (min(off_d, rec_dur[r]) - max(on_d, 0)) / dur_d >= cttc: counts[class(d)][C] += 1
+ *         (the world column, a false positive).
+ * A term with inter <= 0 adds nothing, so only items that can overlap are walked, the kept terms in the stated order: the references
+ * from the first j with ref_pmax[j] > on_d (binary search) while ref_on[j] < off_d; the detections from the first d with max(on_d,
+ * off_d) > on_g (binary search; the detections are disjoint) while on_d < off_g.  A reference that spans the recording makes every
+ * scan of its class start at it: time, not correctness.
+ * pass [K][R][C][ceil(cap / 64)] uint64: workspace of the launch (the DTC pass bits of every 64 detections; the wave that writes a word
+ *   is the only one that reads it).  8-byte aligned; its contents before and after the launch mean nothing.
+ * counts [n_fusion][K][C][C + 1] int64, row `fusion`: sedt_psds_update's layout, accumulated with integer atomics only (zero them per
+ *   evaluation): two runs give equal bytes.
+ * status [K][R] int32, written by every launch: 0; 1 the stitch status of (k, r) is non-zero or some count[k][r][c] > cap; 4 a list holds
+ *   a non-finite time, is not ascending by onset, or estimates overlap (an onset before the previous offset) - 1 before 4.  With a
+ *   status raised the counters may hold partial sums of that recording.  count is clamped to 0 .. cap before it indexes anything, the
+ *   CSR offsets are clamped to the table: nothing is read or written out of bounds in any case.
+ * 1 <= C <= 63, 1 <= K <= 1024, R >= 0 (R == 0 launches nothing), cap >= 1; dtc, gtc, cttc not NaN. */
+int sedt_recording_psds_counts(const int32_t* count, const int32_t* out, const int32_t* stitch_status, const int32_t* rec_idx,
+                               const int32_t* ref_off, const double* ref_on, const double* ref_end, const double* ref_pmax,
+                               const double* rec_dur, int n_ref_rec, int n_ref_events, int K, int R, int C, int cap, int n_fusion,
+                               int fusion, double dtc, double gtc, double cttc, uint64_t* pass, int64_t* counts, int32_t* status,
+                               void* stream);
 
 /* ------------------------------------------------------------------ input side on the device (utilities/BoxTransforms.py,
  * utilities/mixup.py)

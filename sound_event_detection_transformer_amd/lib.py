@@ -233,6 +233,7 @@ SIGNATURES = {
     'sedt_stitch_events': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp]),
     'sedt_recording_event_counts': (_i, [_vp] * 7 + [_i] * 8 + [_d, _d, _i, _vp, _vp, _vp, _vp]),
     'sedt_recording_segment_counts': (_i, [_vp] * 8 + [_i] * 8 + [_d, _vp, _vp, _vp, _vp]),
+    'sedt_recording_psds_counts': (_i, [_vp] * 9 + [_i] * 8 + [_d, _d, _d, _vp, _vp, _vp, _vp]),
     'sedt_hungarian_batch': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'sedt_adamw_clip': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _i, _vp]),
 }

@@ -2059,6 +2059,31 @@ def recording_segment_counts(count, out, stitch_status, cap, rec_idx, table, n_w
     return status
 
 
+def recording_psds_counts(count, out, stitch_status, cap, rec_idx, table, rec_dur, counts, fusion, dtc=0.5, gtc=0.5, cttc=0.3,
+                          pass_words=None, status=None):
+    """the PSDS confusion counts of one fusion strategy's stitched event lists (stitch_events' count [K,R,C], out [K,R,C,cap,8], status
+    [K,R] and cap) against the recordings' annotations, accumulated into counts int64 [n_fusion, K, C, C + 1] at row ``fusion``: psds_update's
+    layout (include/sedt_hip.h: sedt_recording_psds_counts).  rec_idx and table as recording_event_counts, the table with 'pmax' float64
+    [n_events]: per (recording, class) list the running maximum of 'end'; rec_dur float64 [R]: the recordings' lengths in seconds;
+    pass_words int64 [>= K * R * C * ceil(cap / 64)]: the launch's workspace (allocated when None).  Returns status int32 [K, R]
+    (``status`` when given).  Nothing is read back."""
+    K, R, C, nf, status = _recording_args(count, out, stitch_status, cap, rec_idx, table, (counts,), status)
+    _dev_check(table['pmax'], rec_dur, pass_words)
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (nf, K, C, C + 1) and counts.is_contiguous()
+    assert table['pmax'].dtype == torch.float64 and table['pmax'].numel() >= int(table['n_events']) and table['pmax'].is_contiguous()
+    assert rec_dur.dtype == torch.float64 and rec_dur.numel() == R and rec_dur.is_contiguous()
+    n_pass = K * R * C * ((int(cap) + 63) // 64)
+    if pass_words is None:
+        pass_words = torch.empty(max(n_pass, 1), device=count.device, dtype=torch.int64)
+    assert pass_words.dtype == torch.int64 and pass_words.numel() >= n_pass and pass_words.is_contiguous()
+    L.check(L.load().sedt_recording_psds_counts(_p(count), _p(out), _p(stitch_status), _p(rec_idx), _p(table['off']), _p(table['on']),
+                                                _p(table['end']), _p(table['pmax']), _p(rec_dur), int(table['n_rec']),
+                                                int(table['n_events']), K, R, C, int(cap), nf, int(fusion), float(dtc), float(gtc),
+                                                float(cttc), _p(pass_words), _p(counts), _p(status), L.stream_ptr()),
+            'recording_psds_counts')
+    return status
+
+
 def mixup(x1, x2, jobs, out=None):
     """feature half of utilities/mixup.py: out[i] = lam * x1[src1] + (1 - lam) * x2[src2] / x1[src1] / x2[src2] per job record
     (jobs: uint8 device tensor of n 16-byte records {int32 src1, src2, mode; f32 lam}); x1 / x2 / out f32 [*, clip...]"""

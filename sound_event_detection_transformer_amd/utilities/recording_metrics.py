@@ -252,3 +252,26 @@ class RecordingMetrics(object):
         class tuned on recordings, without a criterion"""
         ev = self.counts()[0][self.fusion.index(m)]
         return select_class_wise(ev, self.decoder.threshold_values.copy(), default)
+
+
+class MetricGroup(object):
+    """several consumers of one detector pass's stitched lists behind the interface ``RecordingDetector.submit(..., metrics=)`` and
+    ``engine.evaluate_recordings`` call - a RecordingMetrics and a utilities.recording_psds.RecordingPsds, say, each with its reference
+    set: ``reset`` and ``update`` go to every member in order, ``compute`` returns the tuple of the members' results."""
+
+    def __init__(self, *metrics):
+        if not metrics:
+            raise ValueError('MetricGroup: no members')
+        self.metrics = tuple(metrics)
+
+    def reset(self):
+        for m in self.metrics:
+            m.reset()
+        return self
+
+    def update(self, stitched, cap, filenames, durations=None):
+        for m in self.metrics:
+            m.update(stitched, cap, filenames, durations=durations)
+
+    def compute(self):
+        return tuple(m.compute() for m in self.metrics)
