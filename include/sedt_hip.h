@@ -44,6 +44,8 @@
  *   sedt_recording_event_counts / sedt_recording_segment_counts               no counterpart: those lists against a recording's annotations,
  *                                                                             sed_eval's event- and segment-based counts at every threshold
  *   sedt_recording_psds_counts                                                no counterpart: PSDS confusion counts from those lists
+ *   sedt_cut_clips                                                            no counterpart as a kernel: training windows and their
+ *                                                                             target tables cut from recordings on the device
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -1123,6 +1125,35 @@ int sedt_mel_spectrogram(const void* wave, int wave_dtype, int64_t wave_stride, 
 int sedt_resample_ok(int L, int M, int taps, int H, int max_channels, int64_t max_in);
 int sedt_resample(const int64_t* desc, int B, int64_t max_out, const float* table, int L, int M, int taps, int H, int max_channels,
                   int64_t max_in, void* stream);
+/* sedt_cut_clips (no counterpart as a kernel: the reference cuts its 10 s clips and encodes their strong labels on the host,
+ * data_utils/DataLoad.py and utilities/BoxEncoder.py encode_strong_df; DESIGN.md section 4, "Training on recordings"): a training batch
+ * cut from annotated recordings that live on the device, in ONE launch - the windows and the windows' target tables.
+ * Inputs: flat f32 [flat_len], the recordings one behind the other; rec_off / rec_len int64 [n_rec], recording r = flat[rec_off[r] ..
+ * rec_off[r] + rec_len[r]); the picks pick_rec int32 [B], pick_start int64 [B] (any sample index >= 0); window samples per clip; sr.
+ * Event table, per recording sorted by (onset, offset, input order): ev_off int32 [n_rec + 1], ev_on / ev_end float64 seconds, ev_cls
+ * int32, ev_pmax float64 = the running maximum of ev_end inside the recording, [n_events] each (at least one element allocated).
+ * wave f32 [B][window]: row b = samples pick_start[b] .. pick_start[b] + window - 1 of recording pick_rec[b], bit for bit; positions past
+ *   the recording's end are 0.  The source is only 4-byte aligned: 16-byte loads where its address allows them.
+ * targets, float64 with plain subtract / multiply / divide / compare (no contraction): W = window / sr, t0 = pick_start[b] / sr,
+ *   t1 = t0 + W; for every event (c, on, end) of the recording in table order a = max(on, t0) - t0, z = min(end, t1) - t0; kept iff
+ *   z - a > 0 and z - a >= min_event_seconds; label c (int64), box (float32(((a + z) * 0.5) / W), float32((z - a) / W)).  Events of
+ *   one class that overlap are kept as annotated.  Two binary searches bound the scan (first ev_pmax > t0, first ev_on >= t1), so a
+ *   recording may hold any number of events.
+ * blob (8-byte aligned, 8 B + 16 + 16 B max_targets bytes): the layout of sedt.TargetTables(batch=B, ns=B, n_lab=B, max_targets,
+ *   with_ratio=False) - int32 lab_off [B + 1] | box_off [B + 1] | B | B, then lab_cat int64 [B max_targets], then box_cat f32
+ *   [B max_targets][2]; lab_off == box_off, exclusive scans over the clips made inside the launch.  Only live entries are written.
+ * status int32 [B]: 0; 1 more than max_targets events survive in the clip - the first max_targets in table order are written; 2 the
+ *   pick is not inside the table (pick_rec outside 0 .. n_rec - 1 or pick_start < 0): a row of zeros and no events.
+ * Offsets, lengths and event ranges are clamped to flat_len / n_events before they index anything.  No allocation, no
+ * synchronisation, no atomics; capturable.  Grid: B * ceil(window / SEDT_CLIPS_CHUNK) workgroups copy, one more owns the targets.
+ * Envelope: 1 <= B <= SEDT_CLIPS_MAXB, 1 <= max_targets <= 63, 1 <= window < 2^31, sr >= 1, n_rec >= 1; outside it, with a NaN
+ * min_event_seconds or a null pointer, the call returns non-zero with a message before it touches a pointer. */
+#define SEDT_CLIPS_MAXB 1024
+#define SEDT_CLIPS_CHUNK 2048
+int sedt_cut_clips(const float* flat, int64_t flat_len, const int64_t* rec_off, const int64_t* rec_len, int n_rec,
+                   const int32_t* pick_rec, const int64_t* pick_start, int B, int64_t window, int sr, const int32_t* ev_off,
+                   const double* ev_on, const double* ev_end, const int32_t* ev_cls, const double* ev_pmax, int n_events, int max_targets,
+                   double min_event_seconds, float* wave, void* blob, int32_t* status, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

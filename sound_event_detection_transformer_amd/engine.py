@@ -646,8 +646,13 @@ class GraphedTrainStep(_GraphedBase):
     def __call__(self, batch_input, targets, check_finite=False, patches=None):
         """one step on (batch_input, targets).  With mix-up the batch arrives UNMIXED in the layout the stepper was built with
         (strong clips, then weak ones); the np.random draws, the label bookkeeping and the new split happen here on the host
-        (utilities.mixup.plan_mixup_data), the feature mixing inside the graph.  Keep the targets on the host for that."""
+        (utilities.mixup.plan_mixup_data), the feature mixing inside the graph.  Keep the targets on the host for that.
+        ``targets`` may be a utilities.recording_clips.DeviceTargets (every clip strong, built on the device by the launch that cut the
+        clips): the tables are then filled by one device copy - device matching without mix-up only."""
         split = {}
+        if hasattr(targets, 'blob') and (self.mix or not self.device_matching):
+            raise NotImplementedError('targets built on the device (DeviceTargets) feed the device-matching graph without mix-up only: the '
+                                      'host plans of mix-up and of the host matching need the labels; pass targets.to_list()')
         if self.mix:
             from .utilities.mixup import draw_mixup_data, plan_mixup_data, job_table
             import numpy as np
@@ -960,6 +965,27 @@ def evaluate_recordings(detector, metrics, calls):
     for call in calls:
         detector.submit(call[0], call[1], call[2] if len(call) > 2 else None, metrics=metrics)
     return metrics.compute()
+
+
+def train_on_recordings(step, clips, transform, steps, batch_size=None):
+    """the plain training loop on annotated recordings that live on the device: ``step`` a GraphedTrainStep (device matching, no
+    mix-up, its tables built with the clips' max_targets), ``clips`` a utilities.recording_clips.RecordingClips with its recordings
+    added, ``transform`` a DeviceBoxTransform (it may augment).  Per step: clips.draw (np.random on the host), ONE sedt_cut_clips
+    launch for the windows and their target tables, mel, transform, one replay - nothing is read back inside the loop.  The clips'
+    statuses are logged on the device and checked ONCE at the end: a clip with more events than max_targets raises, naming step
+    and recording.  Returns the last step's (total, losses): the stepper's static tensors."""
+    from .utilities.recording_clips import status_error
+    B = int(step.static_x.shape[0]) if batch_size is None else int(batch_size)
+    log = torch.zeros((max(int(steps), 1), B), dtype=torch.int32, device=clips.dev)
+    names, out = [], None
+    for i in range(int(steps)):
+        x, targets = clips.batch(transform, clips.draw(B), status=log[i])
+        names.append(targets.names)
+        out = step(x, targets)
+    err = status_error(log[:len(names)].cpu().numpy(), names, 'train_on_recordings') if names else None
+    if err is not None:
+        raise err
+    return out
 
 
 def evaluate_events(model, criterion, postprocessor, batches, metrics, at=True, threshold=0.5, graphed=True, max_targets=32):
@@ -1315,6 +1341,9 @@ class GraphedSemiStep(_GraphedBase):
         self.ema.update()
 
     def __call__(self, x_teacher, x_student, targets, check_finite=False):
+        if hasattr(targets, 'blob'):
+            raise NotImplementedError('GraphedSemiStep: targets built on the device (DeviceTargets) are every clip strong and cannot be '
+                                      'split into labelled | unlabelled on the host; pass a list of target dicts')
         xt, xs = _tensors(x_teacher), _tensors(x_student)
         self.x_tea.copy_(xt[self.mu], non_blocking=True)
         if self.mix:

@@ -16,6 +16,7 @@ BF16X3 = 2            # GEMM entry points only: f32 tensors, split-bf16 products
 I16 = 3               # sedt_mel_spectrogram and sedt_resample only: the waveform as 16-bit PCM
 RESAMPLE_BLK = 1024   # sedt_resample: outputs per workgroup (SEDT_RESAMPLE_BLK)
 RESAMPLE_DESC_WORDS = 6
+CLIPS_MAXB = 1024      # sedt_cut_clips: clips per launch (SEDT_CLIPS_MAXB)
 GEMM_X3 = False       # runtime.set_compute_dtype('bf16x3'): the f32 mode's contractions go through the BF16X3 code
 
 
@@ -217,6 +218,7 @@ SIGNATURES = {
     'sedt_mel_spectrogram': (_i, [_vp, _i, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'sedt_resample_ok': (_i, [_i, _i, _i, _i, _i, _i64]),
     'sedt_resample': (_i, [_vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _i64, _vp]),
+    'sedt_cut_clips': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _i64, _i] + [_vp] * 5 + [_i, _i, _d, _vp, _vp, _vp, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_query_patches': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),

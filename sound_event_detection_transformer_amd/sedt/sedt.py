@@ -242,6 +242,8 @@ class TargetTables(object):
         B = self.B
         if len(targets) != B:
             raise ValueError(f'expected {B} clips, got {len(targets)}')
+        if hasattr(targets, 'blob'):
+            return self._load_device(targets)
         if ns is not None or n_lab is not None:
             if not self.dynamic:
                 if (ns, n_lab) != (self.cur_ns, self.cur_n_lab):
@@ -314,6 +316,24 @@ class TargetTables(object):
             src = targets[0]['labels'].device
             self.ratio_cat[:nl].copy_(torch.cat([t['ratio'].detach().float().reshape(-1).to(src) if 'ratio' in t else
                                                  torch.ones(n, device=src) for t, n in zip(targets, nlab)]), non_blocking=True)
+        return self
+
+
+    def _load_device(self, targets):
+        """targets built on the device (utilities.recording_clips.DeviceTargets: every clip strong, the blob already in this layout):
+        ONE asynchronous device copy, nothing is read back.  A ratio table is refilled with ones."""
+        if self.dynamic:
+            raise NotImplementedError('targets built on the device cannot feed dynamic-split tables (mix-up): the host plan of the '
+                                      'merged batch needs the labels; pass targets.to_list()')
+        if not (self.ns == self.n_lab == self.B) or targets.max_targets != self.max_targets:
+            raise ValueError(f'targets built on the device are {targets.B} strong clips of up to {targets.max_targets} events; these '
+                             f'tables hold {self.ns} strong | {self.n_lab} labelled of {self.B} clips, max_targets={self.max_targets}')
+        o_rat = self._lay[5]
+        if targets.blob.numel() != o_rat or targets.blob.device != self._blob.device:
+            raise ValueError('targets built on the device: the blob does not have this table layout')
+        self._blob[:o_rat].copy_(targets.blob, non_blocking=True)
+        if self.ratio_cat is not None:
+            self.ratio_cat.fill_(1.0)
         return self
 
 

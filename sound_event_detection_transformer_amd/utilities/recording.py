@@ -61,6 +61,64 @@ def check_output_bytes(K, R, C, cap):
     return nbytes
 
 
+def stage_resampled(waves, sample_rates, resampler, dev):
+    """stage_recordings for recordings at their own sample rates, 1-D or interleaved (frames, channels); ``resampler``: rate -> the
+    DeviceResampler from that rate to the model's (kept by the caller).  Grouped by rate, every group ONE
+    sedt_resample launch that down-mixes, converts to mel.sr and writes straight into the flat vector at the recordings'
+    offsets (a recording already at mel.sr goes through the identity plan).  Lengths and offsets are the resampled ones."""
+    rates = [int(sample_rates)] * len(waves) if np.ndim(sample_rates) == 0 else [int(r) for r in sample_rates]
+    if len(rates) != len(waves):
+        raise ValueError('sample_rates: one rate, or one per recording')
+    groups = {}
+    for i, r in enumerate(rates):
+        groups.setdefault(r, []).append(i)
+    staged, ns = {}, [0] * len(waves)
+    for r, idx in groups.items():
+        rs = resampler(r)
+        clips, pins = rs.stage([waves[i] for i in idx])
+        staged[r] = (rs, clips, pins)
+        for i, (_, n, _) in zip(idx, clips):
+            ns[i] = rs.n_out(n)
+    off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    flat = torch.empty(max(int(off[-1]), 1), dtype=torch.float32, device=dev)
+    for r, idx in groups.items():
+        rs, clips, _ = staged[r]
+        rs.launch(clips, flat, [int(off[i]) for i in idx], [ns[i] for i in idx])
+    return flat, off, ns, [(clips, pins) for _, clips, pins in staged.values()]     # the raw input lives as long as the flat vector
+
+
+def stage_recordings(waves, dev):
+    """the recordings as ONE float32 device vector (every recording 4-byte aligned by construction) and their sample offsets.
+    Host waveforms go through one pinned buffer; int16 PCM is widened as the mel kernel widens it (x / 32768, exact).
+    Returns (flat, offsets int64 [R + 1], samples per recording, what must stay alive until the copies have run).
+    Shared by RecordingDetector and recording_clips.RecordingClips."""
+    ns = [int(w.shape[0]) for w in waves]
+    if any(getattr(w, 'ndim', 1) != 1 for w in waves):
+        raise ValueError('mono waveforms expected: every recording 1-D (pass sample_rates= to down-mix and resample on the device)')
+    off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    flat = torch.empty(max(int(off[-1]), 1), dtype=torch.float32, device=dev)
+    host = None
+    if any(not (torch.is_tensor(w) and w.is_cuda) for w in waves):
+        host = torch.empty(max(int(off[-1]), 1), dtype=torch.float32).pin_memory()
+    for i, w in enumerate(waves):
+        dst = slice(int(off[i]), int(off[i + 1]))
+        if torch.is_tensor(w) and w.is_cuda:
+            flat[dst] = w.float() * (1.0 / 32768.0) if w.dtype == torch.int16 else w.float()
+        else:
+            a = w.numpy() if torch.is_tensor(w) else np.asarray(w)
+            if a.dtype == np.int16:
+                a = a.astype(np.float32) * np.float32(1.0 / 32768.0)
+            elif a.dtype != np.float32:
+                raise ValueError(f'waveforms are float32 or int16, got {a.dtype}')
+            host.numpy()[dst] = a
+    if host is not None:
+        for i, w in enumerate(waves):
+            if not (torch.is_tensor(w) and w.is_cuda):
+                dst = slice(int(off[i]), int(off[i + 1]))
+                flat[dst].copy_(host[dst], non_blocking=True)
+    return flat, off, ns, host
+
+
 class WindowTags(object):
     """the audio tags of every window of a call with the window table: ``tags`` (W, C) 0/1 (None without audio tagging),
     ``recording`` (W,) index into ``filenames``, ``start`` (W,) float64 seconds"""
@@ -205,60 +263,15 @@ class RecordingDetector(object):
         return rs
 
     def _stage_resampled(self, waves, sample_rates):
-        """_stage for recordings at their own sample rates, 1-D or interleaved (frames, channels): grouped by rate, every group ONE
-        sedt_resample launch that down-mixes, converts to mel.sr and writes straight into the flat vector at the recordings'
-        offsets (a recording already at mel.sr goes through the identity plan).  Lengths and offsets are the resampled ones."""
-        rates = [int(sample_rates)] * len(waves) if np.ndim(sample_rates) == 0 else [int(r) for r in sample_rates]
-        if len(rates) != len(waves):
-            raise ValueError('sample_rates: one rate, or one per recording')
-        groups = {}
-        for i, r in enumerate(rates):
-            groups.setdefault(r, []).append(i)
-        staged, ns = {}, [0] * len(waves)
-        for r, idx in groups.items():
-            rs = self.resampler(r)
-            clips, pins = rs.stage([waves[i] for i in idx])
-            staged[r] = (rs, clips, pins)
-            for i, (_, n, _) in zip(idx, clips):
-                ns[i] = rs.n_out(n)
-        off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
-        flat = torch.empty(max(int(off[-1]), 1), dtype=torch.float32, device=self.dev)
-        for r, idx in groups.items():
-            rs, clips, _ = staged[r]
-            rs.launch(clips, flat, [int(off[i]) for i in idx], [ns[i] for i in idx])
-        return flat, off, ns, [(clips, pins) for _, clips, pins in staged.values()]     # the raw input lives as long as the flat vector
+        """_stage for recordings at their own sample rates: stage_resampled with this detector's resamplers"""
+        return stage_resampled(waves, sample_rates, self.resampler, self.dev)
 
     def _stage(self, waves, sample_rates=None):
-        """the recordings as ONE float32 device vector (every recording 4-byte aligned by construction) and their sample offsets.
-        Host waveforms go through one pinned buffer; int16 PCM is widened as the mel kernel widens it (x / 32768, exact).
-        With ``sample_rates``: _stage_resampled."""
+        """the recordings as ONE float32 device vector and their sample offsets (stage_recordings; with ``sample_rates``:
+        _stage_resampled)"""
         if sample_rates is not None:
             return self._stage_resampled(waves, sample_rates)
-        ns = [int(w.shape[0]) for w in waves]
-        if any(getattr(w, 'ndim', 1) != 1 for w in waves):
-            raise ValueError('mono waveforms expected: every recording 1-D (pass sample_rates= to down-mix and resample on the device)')
-        off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
-        flat = torch.empty(max(int(off[-1]), 1), dtype=torch.float32, device=self.dev)
-        host = None
-        if any(not (torch.is_tensor(w) and w.is_cuda) for w in waves):
-            host = torch.empty(max(int(off[-1]), 1), dtype=torch.float32).pin_memory()
-        for i, w in enumerate(waves):
-            dst = slice(int(off[i]), int(off[i + 1]))
-            if torch.is_tensor(w) and w.is_cuda:
-                flat[dst] = w.float() * (1.0 / 32768.0) if w.dtype == torch.int16 else w.float()
-            else:
-                a = w.numpy() if torch.is_tensor(w) else np.asarray(w)
-                if a.dtype == np.int16:
-                    a = a.astype(np.float32) * np.float32(1.0 / 32768.0)
-                elif a.dtype != np.float32:
-                    raise ValueError(f'waveforms are float32 or int16, got {a.dtype}')
-                host.numpy()[dst] = a
-        if host is not None:
-            for i, w in enumerate(waves):
-                if not (torch.is_tensor(w) and w.is_cuda):
-                    dst = slice(int(off[i]), int(off[i + 1]))
-                    flat[dst].copy_(host[dst], non_blocking=True)
-        return flat, off, ns, host
+        return stage_recordings(waves, self.dev)
 
     def _cut_jobs(self, flat, rec_off, ns, win_off, start, lo, hi):
         """the copy2d jobs that fill rows 0 .. hi - lo - 1 of self.wave with windows lo .. hi - 1: runs of windows of one recording a
