@@ -46,6 +46,7 @@
  *   sedt_recording_psds_counts                                                no counterpart: PSDS confusion counts from those lists
  *   sedt_cut_clips                                                            no counterpart as a kernel: training windows and their
  *                                                                             target tables cut from recordings on the device
+ *   sedt_mixup_plan                                                           mixup_data's label half  utilities/mixup.py:30-127
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
  *   sedt_multi_gather                                                         DDP gradient buckets  train_spsedt.py:157-158
@@ -1168,6 +1169,35 @@ int sedt_mixup_targets(const int64_t* lab1, const int32_t* lab_off1, const float
                        const int32_t* box_off2, int B2, const float* lam, int mix_num, int max_events, int64_t* lab_out,
                        int32_t* lab_off_out, float* box_out, int32_t* box_off_out, float* ratio_out, int cap, void* jobs,
                        void* stream);
+/* sedt_mixup_plan: the LABEL half of mixup_data (utilities/mixup.py:13-127; call sites engine.py:50-53 and 128-133) for a batch whose
+ * targets were built on the device - the device restatement of utilities.mixup.plan_mixup_data ("Mix-up and
+ * mean-teacher training on recordings").
+ * Source: src_blob in the layout sedt_cut_clips writes for B_src all-strong clips of up to max_targets_src events, of which the first B
+ * are used under the static split 0 <= ns <= n_lab <= B: clip b has nl(b) labels (0 when b >= n_lab) and nb(b) boxes (0 when b >= ns:
+ * a weak clip's boxes are ignored).  index int32 [B] and lam f32 [2] = {lam, 1 - lam} as the host rounds them are device-resident and
+ * drawn on the host (utilities.mixup.draw_mixup_data, lam_pair).  For i < mix_num, j = index[i], n1 = nb(i), n2 = nb(j), the first row
+ * that applies decides:
+ *   n1 == 0 or n2 == 0, and n1 > 0      keep-1: target i, job {i, 0, 1, 0}
+ *   n1 == 0 or n2 == 0, and n2 > 0      keep-2: target j, job {0, j, 2, 0}
+ *   n1 == 0 and n2 == 0                 weak merge: labels of i then of j, no boxes, ratio lam x nl(i) then (1 - lam) x nl(j), job {i, j, 0, lam}
+ *   n1 + n2 > max_events                keep-1
+ *   two boxes of one class overlap anywhere in boxes(i) ++ boxes(j), inside clip i alone included (box k carries label k of
+ *   labels(i) ++ labels(j); s = c - l / 2, e = c + l / 2 in f32; a clash iff !(e_j < s_k) && !(e_k < s_j))      keep-1
+ *   none of the above                   strong merge: labels, boxes, ratios concatenated, job {i, j, 0, lam}
+ * Output order: the keeps and strong merges in order of i; clips mix_num .. ns - 1; the weak merges in order of i; clips ns ..
+ * n_lab - 1; clips n_lab .. B - 1.  Unchanged clips get job {b, 0, 1, 0} and ratio 1.
+ * out_blob: the dynamic-split TargetTables layout of B clips with ratio - int32 lab_off [B + 1] | box_off [B + 1] | ns' | n_lab, at
+ * byte 8 B + 16 lab_cat int64 [B max_targets_out], box_cat f32 [B max_targets_out][2], ratio_cat f32 [B max_targets_out]; ns' = ns -
+ * #weak merges; box_off is flat beyond ns'; only live entries are written.  jobs: B sedt_mixup records.  status int32 [B], indexed by
+ * the SOURCE clip a result belongs to (i for the mixed clips, keep-2 included): 0; 1 the result holds more than max_targets_out labels
+ * (the first max_targets_out are written); 2 index[i] is outside 0 .. B - 1 (treated as keep-1).
+ * One workgroup; no atomics, no allocation, no synchronisation; deterministic and capturable; source offsets are clamped to the
+ * source tables before they index anything.  Envelope: 1 <= B <= B_src <= 1024, 0 <= ns <= n_lab <= B, 0 <= mix_num <= ns (the batch
+ * then never shrinks: exactly B results on every draw), 1 <= max_events <= max_targets_out <= 63, 1 <= max_targets_src <= 63; outside
+ * it or with a null pointer the call returns non-zero with a message before it touches a pointer. */
+int sedt_mixup_plan(const void* src_blob, int B_src, int max_targets_src, int B, int ns, int n_lab, const int32_t* index,
+                    const float* lam, int mix_num, int max_events, int max_targets_out, void* out_blob, void* jobs, int32_t* status,
+                    void* stream);
 
 /* SP-SEDT query patches (utilities/BoxTransforms.py:315-360, Query.transform_label; boxes from DataLoad.py:57-77 are turned into
  * row ranges on the host): for each of n_patches jobs {clip, s_idx, e_idx, 0} (int32 x 4, device memory) crop rows [s_idx, e_idx)

@@ -643,17 +643,35 @@ class GraphedTrainStep(_GraphedBase):
         else:                                                # all gradients -> one flat buffer (one launch)
             self.flat_parts = [self.optimizer.gather_grads(accumulate=self.accum_steps > 1)]
 
-    def __call__(self, batch_input, targets, check_finite=False, patches=None):
+    def __call__(self, batch_input, targets, check_finite=False, patches=None, plan_status=None):
         """one step on (batch_input, targets).  With mix-up the batch arrives UNMIXED in the layout the stepper was built with
         (strong clips, then weak ones); the np.random draws, the label bookkeeping and the new split happen here on the host
-        (utilities.mixup.plan_mixup_data), the feature mixing inside the graph.  Keep the targets on the host for that.
-        ``targets`` may be a utilities.recording_clips.DeviceTargets (every clip strong, built on the device by the launch that cut the
-        clips): the tables are then filled by one device copy - device matching without mix-up only."""
+        (utilities.mixup.plan_mixup_data), the feature mixing inside the graph.
+        ``targets`` may be a utilities.recording_clips.DeviceTargets (built on the device by the launch that cut the clips, with the
+        stepper's strong | weak split): the tables are then filled by device copies, and with mix-up the draws stay on the host
+        (draw_mixup_data: the reference's np.random order) while the label bookkeeping is ONE launch (TargetTables.load_mixed,
+        sedt_mixup_plan) that also writes the job records of the feature mixing; ``plan_status``: an int32 [B] device tensor for its
+        statuses.  That needs device matching, a weak mask (an empty slice(ns, ns) will do) and int(B * mix_up_ratio) <= the number of
+        strong clips: without a weak mask the reference drops clips on some draws, which only a read-back could tell."""
         split = {}
-        if hasattr(targets, 'blob') and (self.mix or not self.device_matching):
+        on_device = hasattr(targets, 'blob')
+        if on_device and (not self.device_matching or (self.mix and self.mw is None)):
             raise NotImplementedError('targets built on the device (DeviceTargets) feed the device-matching graph without mix-up only: the '
                                       'host plans of mix-up and of the host matching need the labels; pass targets.to_list()')
-        if self.mix:
+        if self.mix and on_device:
+            from .utilities.mixup import draw_mixup_data
+            B = self.tables.B
+            want = (len(range(*self.ms.indices(B))), int(self.mw.stop))
+            if len(targets) != B or (targets.ns, targets.n_lab) != want:
+                raise ValueError(f'targets built on the device are {targets.ns} strong | {targets.n_lab} labelled of {len(targets)} clips; '
+                                 f'the stepper was built for {want[0]} | {want[1]} of {B}')
+            mix_num = int(B * self.mix)
+            if mix_num > targets.ns:
+                raise ValueError(f'mix-up of the first int({B} * {self.mix}) = {mix_num} clips needs as many strong clips, the batch has '
+                                 f'{targets.ns}: pass targets.to_list() or lower mix_up_ratio')
+            lam, index = draw_mixup_data(B, self.mix_alpha)
+            self.static_raw.copy_(batch_input, non_blocking=True)
+        elif self.mix:
             from .utilities.mixup import draw_mixup_data, plan_mixup_data, job_table
             import numpy as np
             rng = np.random.get_state()
@@ -677,7 +695,10 @@ class GraphedTrainStep(_GraphedBase):
             self.runtime.bump_seed(self.dev)
         self._before_replay()
         if self.device_matching:
-            self.tables.load(targets, **split)
+            if self.mix and on_device:
+                self.tables.load_mixed(targets, lam, index, mix_num, self.max_events, self._jobs.dev_buf, status=plan_status)
+            else:
+                self.tables.load(targets, **split)
             self.g_fwd.replay()
         else:
             self.g_fwd.replay()
@@ -967,22 +988,69 @@ def evaluate_recordings(detector, metrics, calls):
     return metrics.compute()
 
 
-def train_on_recordings(step, clips, transform, steps, batch_size=None):
-    """the plain training loop on annotated recordings that live on the device: ``step`` a GraphedTrainStep (device matching, no
-    mix-up, its tables built with the clips' max_targets), ``clips`` a utilities.recording_clips.RecordingClips with its recordings
-    added, ``transform`` a DeviceBoxTransform (it may augment).  Per step: clips.draw (np.random on the host), ONE sedt_cut_clips
-    launch for the windows and their target tables, mel, transform, one replay - nothing is read back inside the loop.  The clips'
-    statuses are logged on the device and checked ONCE at the end: a clip with more events than max_targets raises, naming step
-    and recording.  Returns the last step's (total, losses): the stepper's static tensors."""
+PLAN_STATUS_REASONS = {1: 'the mixed clip holds more labels than max_targets: build the tables with a larger max_targets',
+                       2: 'the mix-up partner is not a clip of the batch'}
+
+
+def _recording_loop_error(what, cut_log, plan_log, names):
+    """the RuntimeError of the first raised status of a recording loop's device logs (read here, once), or None"""
     from .utilities.recording_clips import status_error
+    if not names:
+        return None
+    err = status_error(cut_log[:len(names)].cpu().numpy(), names, what)
+    if err is None and plan_log is not None:
+        err = status_error(plan_log[:len(names)].cpu().numpy(), names, what + ', mix-up plan', PLAN_STATUS_REASONS)
+    return err
+
+
+def train_on_recordings(step, clips, transform, steps, batch_size=None, split=None):
+    """the training loop on recordings that live on the device: ``step`` a GraphedTrainStep (device matching, its tables built with the
+    clips' max_targets; with or without mix-up), ``clips`` a utilities.recording_clips.RecordingClips with its recordings added,
+    ``transform`` a DeviceBoxTransform (it may augment).  ``split`` = (n_strong, n_weak): the batch is that many clips of strong, then
+    of weak recordings (clips.draw_split) - the stepper's masks; default: every clip strong (clips.draw).  Per step: the picks
+    (np.random on the host), ONE sedt_cut_clips launch for the windows and their target tables, mel, transform, with mix-up the host
+    draws and ONE sedt_mixup_plan launch, one replay - nothing is read back inside the loop.  The statuses of the cuts and of the plans
+    are logged on the device and checked ONCE at the end: a clip with more events than max_targets raises, naming step and recording.
+    Returns the last step's (total, losses): the stepper's static tensors."""
     B = int(step.static_x.shape[0]) if batch_size is None else int(batch_size)
+    if split is not None and int(split[0]) + int(split[1]) != B:
+        raise ValueError(f'train_on_recordings: split {tuple(split)} is not the batch size {B}')
+    mixing = bool(getattr(step, 'mix', 0))
     log = torch.zeros((max(int(steps), 1), B), dtype=torch.int32, device=clips.dev)
+    plan_log = torch.zeros_like(log) if mixing else None
     names, out = [], None
     for i in range(int(steps)):
-        x, targets = clips.batch(transform, clips.draw(B), status=log[i])
+        if split is None:
+            x, targets = clips.batch(transform, clips.draw(B), status=log[i])
+        else:
+            x, targets = clips.batch(transform, clips.draw_split(int(split[0]), int(split[1])), status=log[i], split=(int(split[0]), B))
         names.append(targets.names)
-        out = step(x, targets)
-    err = status_error(log[:len(names)].cpu().numpy(), names, 'train_on_recordings') if names else None
+        out = step(x, targets, plan_status=plan_log[i]) if mixing else step(x, targets)
+    err = _recording_loop_error('train_on_recordings', log, plan_log, names)
+    if err is not None:
+        raise err
+    return out
+
+
+def semi_train_on_recordings(step, clips, view_transform, steps, split):
+    """the mean-teacher loop on recordings that live on the device: ``step`` a GraphedSemiStep (with or without mix-up, its labelled
+    tables built with the clips' max_targets), ``clips`` a RecordingClips with strong, weak and unlabelled recordings added,
+    ``view_transform`` a DeviceViewTransform, ``split`` = (n_strong, n_weak, n_unlabelled): the stepper's batch layout.  Per step: the
+    picks kind by kind (clips.draw_split), ONE sedt_cut_clips launch for the whole batch, mel, both views in one launch, with mix-up
+    the host draws and ONE sedt_mixup_plan launch, one replay - nothing is read back inside the loop.  The statuses of the cuts and of
+    the plans go to device logs that are read ONCE after the loop: a clip over capacity raises, naming step and recording.  Returns
+    the last step's (total, sup, unsup): the stepper's static tensors."""
+    n_s, n_w, n_u = (int(v) for v in split)
+    B, n_l = n_s + n_w + n_u, n_s + n_w
+    mixing = bool(getattr(step, 'mix', 0))
+    log = torch.zeros((max(int(steps), 1), B), dtype=torch.int32, device=clips.dev)
+    plan_log = torch.zeros((max(int(steps), 1), max(n_l, 1)), dtype=torch.int32, device=clips.dev) if mixing else None
+    names, out = [], None
+    for i in range(int(steps)):
+        (x_t, x_s), targets = clips.batch(view_transform, clips.draw_split(n_s, n_w, n_u), status=log[i], split=(n_s, n_l))
+        names.append(targets.names)
+        out = step(x_t, x_s, targets, plan_status=plan_log[i]) if mixing else step(x_t, x_s, targets)
+    err = _recording_loop_error('semi_train_on_recordings', log, plan_log, names)
     if err is not None:
         raise err
     return out
@@ -1340,13 +1408,32 @@ class GraphedSemiStep(_GraphedBase):
         self._eager_update()                                  # (flat mode: the eager warm-up of the flat-buffer schedule)
         self.ema.update()
 
-    def __call__(self, x_teacher, x_student, targets, check_finite=False):
-        if hasattr(targets, 'blob'):
-            raise NotImplementedError('GraphedSemiStep: targets built on the device (DeviceTargets) are every clip strong and cannot be '
-                                      'split into labelled | unlabelled on the host; pass a list of target dicts')
+    def __call__(self, x_teacher, x_student, targets, check_finite=False, plan_status=None):
+        """one step.  ``targets``: the list of target dicts of the whole batch, or a utilities.recording_clips.DeviceTargets of the whole
+        batch (strong | weak | unlabelled clips, its split the stepper's): the labelled tables are then filled from its first clips on
+        the device - TargetTables.load without mix-up, TargetTables.load_mixed (sedt_mixup_plan; ``plan_status``: an int32 device
+        tensor, one word per labelled clip, for its statuses) with it; the np.random draws are the host route's, in its order."""
         xt, xs = _tensors(x_teacher), _tensors(x_student)
+        on_device = hasattr(targets, 'blob')
+        if on_device:
+            n_l, n_u = self.x_lab.shape[0], self.x_stu.shape[0]
+            want = (len(range(*self.ms.indices(n_l))), n_l)
+            if len(targets) != n_l + n_u or (targets.ns, targets.n_lab) != want:
+                raise ValueError(f'targets built on the device are {targets.ns} strong | {targets.n_lab} labelled of {len(targets)} clips; '
+                                 f'the stepper was built for {want[0]} | {want[1]} of {n_l + n_u}')
+            if self.mix and int(n_l * self.mix) > targets.ns:          # (said before np.random is consumed)
+                raise ValueError(f'mix-up of the first int({n_l} * {self.mix}) = {int(n_l * self.mix)} labelled clips needs as many strong '
+                                 f'clips, the batch has {targets.ns}: pass a list of target dicts or lower mix_up_ratio')
         self.x_tea.copy_(xt[self.mu], non_blocking=True)
-        if self.mix:
+        if self.mix and on_device:
+            from .utilities.mixup import draw_mixup_data, draw_mixup_label_unlabel, lam_pair
+            lam, index = draw_mixup_data(n_l, self.mix_alpha)
+            lam_u = draw_mixup_label_unlabel(self.mix_alpha)
+            self.x_lab_raw.copy_(xt[self.ml], non_blocking=True)
+            self.x_stu_raw.copy_(xs[self.mu], non_blocking=True)
+            self._lam_u.send(torch.from_numpy(lam_pair(lam_u).view(np.uint8).copy()))
+            self.tab_l.load_mixed(targets, lam, index, int(n_l * self.mix), self.max_events, self._jobs_l.dev_buf, status=plan_status)
+        elif self.mix:
             from .utilities.mixup import draw_mixup_data, draw_mixup_label_unlabel, plan_mixup_data, job_table, lam_pair
             lab_t = targets[self.ml]
             lam, index = draw_mixup_data(len(lab_t), self.mix_alpha)            # np.random in the reference's order (mixup.py:22-29,
@@ -1360,7 +1447,7 @@ class GraphedSemiStep(_GraphedBase):
         else:
             self.x_lab.copy_(xt[self.ml], non_blocking=True)
             self.x_stu.copy_(xs[self.mu], non_blocking=True)
-            self.tab_l.load(targets[self.ml])
+            self.tab_l.load(targets if on_device else targets[self.ml])
         if self._host_bump:
             self.runtime.bump_seed(self.dev)
         self._before_replay()

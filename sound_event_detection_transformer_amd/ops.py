@@ -2113,3 +2113,24 @@ def mixup_targets(tab1, tab2, lam, mix_num, tab_out, jobs, max_events=20):
                                         _p(do['box_cat']), _p(do['box_off']), _p(do['ratio_cat']), cap, _p(jobs), L.stream_ptr()),
             'mixup_targets')
     return tab_out
+
+
+def mixup_plan(src_blob, B_src, max_targets_src, B, ns, n_lab, index, lam, mix_num, max_events, max_targets_out, out_blob, jobs, status):
+    """label half of mixup_data (utilities/mixup.py:13-127) on the device - utilities.mixup.plan_mixup_data for targets that were built
+    on the device: src_blob = the uint8 blob sedt_cut_clips wrote for B_src clips of up to max_targets_src events, read under the
+    static split (ns, n_lab) of its first B clips; index int32 [B] and lam f32 [2] {lam, 1 - lam} on the device; writes the merged
+    targets into out_blob (uint8, the dynamic-split TargetTables layout of B clips with ratio, max_targets_out events per clip), the B
+    feature-mixing records into jobs (uint8 [16 * B]) and status int32 [B] (include/sedt_hip.h: sedt_mixup_plan).  ONE launch."""
+    _dev_check(src_blob, index, lam, out_blob, jobs, status)
+    B_src, B, Ms, Mo = int(B_src), int(B), int(max_targets_src), int(max_targets_out)
+    assert src_blob.dtype == torch.uint8 and out_blob.dtype == torch.uint8 and jobs.dtype == torch.uint8
+    assert src_blob.is_contiguous() and out_blob.is_contiguous() and jobs.is_contiguous() and status.is_contiguous()
+    if B >= 1 and B_src >= 1 and Ms >= 1 and Mo >= 1:                      # (the entry point refuses the rest with its own message)
+        assert src_blob.numel() >= 8 * B_src + 16 + 16 * B_src * Ms, 'mixup_plan: the source blob is smaller than its layout'
+        assert out_blob.numel() >= 8 * B + 16 + 20 * B * Mo, 'mixup_plan: the output blob is smaller than the tables with ratio'
+        assert jobs.numel() >= 16 * B and status.dtype == torch.int32 and status.numel() >= B
+        assert index.dtype == torch.int32 and index.numel() >= B and index.is_contiguous()
+        assert lam.dtype == torch.float32 and lam.numel() >= 2 and lam.is_contiguous()
+    L.check(L.load().sedt_mixup_plan(_p(src_blob), B_src, Ms, B, int(ns), int(n_lab), _p(index), _p(lam), int(mix_num), int(max_events),
+                                     Mo, _p(out_blob), _p(jobs), _p(status), L.stream_ptr()), 'mixup_plan')
+    return out_blob

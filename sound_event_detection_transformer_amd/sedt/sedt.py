@@ -240,10 +240,10 @@ class TargetTables(object):
         """ns / n_lab: this batch's split (dynamic_split tables only; default: the previous one)"""
         import numpy as np
         B = self.B
-        if len(targets) != B:
-            raise ValueError(f'expected {B} clips, got {len(targets)}')
         if hasattr(targets, 'blob'):
             return self._load_device(targets)
+        if len(targets) != B:
+            raise ValueError(f'expected {B} clips, got {len(targets)}')
         if ns is not None or n_lab is not None:
             if not self.dynamic:
                 if (ns, n_lab) != (self.cur_ns, self.cur_n_lab):
@@ -320,20 +320,78 @@ class TargetTables(object):
 
 
     def _load_device(self, targets):
-        """targets built on the device (utilities.recording_clips.DeviceTargets: every clip strong, the blob already in this layout):
-        ONE asynchronous device copy, nothing is read back.  A ratio table is refilled with ones."""
+        """targets built on the device (utilities.recording_clips.DeviceTargets: the blob sedt_cut_clips wrote for B_src >= B all-strong
+        clips, read under its static split): asynchronous device copies, nothing is read back.  The labelled clips come first, so every
+        part of these (smaller) tables is a prefix of the source's part: ONE copy when source and tables have the same shape and every
+        clip is strong, else one per part (label offsets, box offsets, labels, boxes).  A ratio table is refilled with ones."""
         if self.dynamic:
-            raise NotImplementedError('targets built on the device cannot feed dynamic-split tables (mix-up): the host plan of the '
-                                      'merged batch needs the labels; pass targets.to_list()')
-        if not (self.ns == self.n_lab == self.B) or targets.max_targets != self.max_targets:
-            raise ValueError(f'targets built on the device are {targets.B} strong clips of up to {targets.max_targets} events; these '
-                             f'tables hold {self.ns} strong | {self.n_lab} labelled of {self.B} clips, max_targets={self.max_targets}')
-        o_rat = self._lay[5]
-        if targets.blob.numel() != o_rat or targets.blob.device != self._blob.device:
+            raise NotImplementedError('targets built on the device cannot be copied into dynamic-split tables (mix-up): the merged batch '
+                                      'is planned from them on the device by load_mixed(); load() is for static-split tables')
+        B, M = self.B, self.max_targets
+        Bs = int(targets.B)
+        ns_src, n_lab_src = min(int(getattr(targets, 'ns', Bs)), B), min(int(getattr(targets, 'n_lab', Bs)), B)
+        if Bs < B or (ns_src, n_lab_src) != (self.ns, self.n_lab) or targets.max_targets != M:
+            raise ValueError(f'targets built on the device are {ns_src} strong | {n_lab_src} labelled of {Bs} clips of up to '
+                             f'{targets.max_targets} events; these tables hold {self.ns} strong | {self.n_lab} labelled of {B} clips, '
+                             f'max_targets={M}')
+        src = targets.blob
+        if src.numel() != 8 * Bs + 16 + 16 * Bs * M or src.device != self._blob.device:
             raise ValueError('targets built on the device: the blob does not have this table layout')
-        self._blob[:o_rat].copy_(targets.blob, non_blocking=True)
+        n_off, o_lab, n_lab_e, o_box, n_box_e, o_rat, total = self._lay
+        if Bs == B and self.ns == B:
+            self._blob[:o_rat].copy_(src, non_blocking=True)
+        else:
+            ns = self.ns
+            so_lab = 8 * Bs + 16
+            so_box = so_lab + 8 * Bs * M
+            self._blob[:4 * (B + 1)].copy_(src[:4 * (B + 1)], non_blocking=True)                              # lab_off [B + 1]
+            self._blob[o_lab:o_lab + 8 * B * M].copy_(src[so_lab:so_lab + 8 * B * M], non_blocking=True)        # a clip holds <= M labels
+            self._blob[4 * (B + 1):4 * (B + ns + 2)].copy_(src[4 * (Bs + 1):4 * (Bs + ns + 2)], non_blocking=True)    # box_off [ns + 1]
+            if ns:
+                self._blob[o_box:o_box + 8 * ns * M].copy_(src[so_box:so_box + 8 * ns * M], non_blocking=True)
         if self.ratio_cat is not None:
             self.ratio_cat.fill_(1.0)
+        return self
+
+    @torch.no_grad()
+    def load_mixed(self, targets, lam, index, mix_num, max_events, jobs, status=None):
+        """the route of targets built on the device into DYNAMIC-split tables: mix-up's label half (utilities.mixup.plan_mixup_data for
+        the draws ``lam``, ``index`` of utilities.mixup.draw_mixup_data) planned ON the device by ONE sedt_mixup_plan launch that reads
+        the first B clips of ``targets`` (a DeviceTargets of B_src >= B clips) under their static split and writes the merged targets
+        and the new split straight into these tables, and the B feature-mixing records into ``jobs`` (uint8 device tensor, >= 16 B bytes:
+        the stepper's job buffer).  ``index`` and ``lam`` travel in one small pinned-ring upload; nothing is read back.
+        ``status``: optional int32 [B] device tensor for the plan's statuses (include/sedt_hip.h), else a buffer of these tables'
+        (``plan_status``).  Needs 0 <= mix_num <= the number of strong clips, so that the batch keeps its size on every draw.
+        The tables' host-side record of the split (the default of a later ``load``) is not updated: the new split exists on the device only."""
+        import numpy as np
+        from .. import ops
+        from ..utilities.mixup import lam_pair
+        from ..utilities.transforms import PinnedRing
+        if not self.dynamic or self.ratio_cat is None:
+            raise ValueError('load_mixed fills dynamic-split tables with ratio: TargetTables(dynamic_split=True, with_ratio=True)')
+        if not hasattr(targets, 'blob'):
+            raise ValueError('load_mixed takes targets built on the device (DeviceTargets); plan host lists with plan_mixup_data and load()')
+        B, Bs = self.B, int(targets.B)
+        if Bs < B:
+            raise ValueError(f'expected at least {B} clips, got {Bs}')
+        ns, n_lab = min(int(targets.ns), B), min(int(targets.n_lab), B)
+        index = np.ascontiguousarray(index, np.int32).reshape(-1)
+        if index.shape[0] != B or (B and (index.min() < 0 or index.max() >= B)):
+            raise ValueError(f'load_mixed: index holds one partner in 0..{B - 1} per clip')
+        if not 0 <= int(mix_num) <= ns:
+            raise ValueError(f'load_mixed: mix-up of the first {mix_num} clips needs as many strong clips, the batch has {ns}: the '
+                             'reference then mixes weak clips as well, which this route does not plan')
+        if not 1 <= int(max_events) <= self.max_targets:
+            raise ValueError(f'load_mixed: max_events={max_events} outside 1..max_targets={self.max_targets}')
+        if self.dev.type != 'cuda' or targets.blob.device != self._blob.device:
+            raise RuntimeError('load_mixed runs on the device (the HIP path has no CPU fallback)')
+        if getattr(self, '_ring', None) is None:
+            self._ring = PinnedRing(self.dev)
+            self.plan_status = torch.zeros(B, dtype=torch.int32, device=self.dev)
+        raw = self._ring.upload(np.concatenate([lam_pair(lam).view(np.uint8), index.view(np.uint8)]))
+        d_lam, d_index = raw[:8].view(torch.float32), raw[8:8 + 4 * B].view(torch.int32)
+        ops.mixup_plan(targets.blob, Bs, targets.max_targets, B, ns, n_lab, d_index, d_lam, int(mix_num), int(max_events),
+                       self.max_targets, self._blob, jobs, self.plan_status if status is None else status)
         return self
 
 

@@ -6,7 +6,9 @@ plain copy for the rest - is ONE launch for the whole output batch (sedt_mixup) 
 Split in two so that a captured step can use it: ``plan_mixup_data`` is the label half (host only: which clip goes where, the
 merged targets, the new strong | weak split) and returns the job records of the feature half; ``mixup_data`` = plan + launch.
 The label half of ``mixup_label_unlabel`` also exists on the device (ops.mixup_targets / sedt_mixup_targets) because inside the
-mean-teacher step its second operand - the pseudo labels - never leaves the device."""
+mean-teacher step its second operand - the pseudo labels - never leaves the device.  ``plan_mixup_data`` has a device restatement too
+(ops.mixup_plan / sedt_mixup_plan, csrc/mixplan.hip) for targets that were built on the device (utilities/recording_clips.py): the draws
+stay here (``draw_mixup_data``), the label bookkeeping is one launch (sedt.TargetTables.load_mixed); the host plan is its oracle."""
 import numpy as np
 import torch
 
