@@ -8,9 +8,10 @@
 //                                 O  += P V      P straight from the S^T accumulators (k-slot s of half h <-> key
 //                                                16u + (s&3) + 8(s>>2) + 4h); the matching V^T fragment is read with
 //                                                ds_read_b64_tr_b16 (same k-slot order), so no cross-lane movement.
-//   backward pass A (32 queries): S^T, dP^T = V dO^T, dS^T = P^T (dP^T - delta)  ->  dQ += dS K   (K^T via tr reads)
-//   backward pass B (32 keys):    S = Q K^T, dP = dO V^T (lane <-> key, registers <-> queries)
+//   backward pass B (32 keys):    S = Q K^T, dP = dO V^T (lane <-> key, registers <-> queries), dS = P (dP - delta)
 //                                 dV^T += dO^T Pd,  dK^T += Q^T dS            (dO^T, Q^T via tr reads)
+//                                 dS also goes, as the bf16 the MFMA reads, into an LDS image [query tile][key][32 queries]
+//   backward dQ phase (32 queries), after one workgroup barrier:  dQ += dS K  (dS and K^T via tr reads of the two images)
 //
 // Probabilities never touch HBM: backward recomputes them from the saved log-sum-exp; the dropout mask is the counter
 // hash of ((b*H+h)*Lq + q)*Lk + k, identical in forward and backward (and to the f32 reference kernels).
@@ -130,6 +131,29 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_mfma_kernel(const bf16_t* __r
 }
 
 // ============================================================================================ backward
+// a thread's 16-byte chunks of one [LP][32] image (chunk u = tid + i * NTHR <-> row u / 4, columns 8 (u % 4) ..), held in registers
+// between the global loads and the LDS stores; rows from L on are stored as zeros (stage_image's layout and padding); 1 <= L <= LP
+template <int LP, int NTHR>
+struct BwdChunks {
+  static constexpr int N = (LP * 4 + NTHR - 1) / NTHR;
+  uint4 r[N];
+  // no branch around a load (the join would wait for it): rows beyond L read row L - 1 and become zeros on their way to LDS
+  __device__ __forceinline__ void load(const bf16_t* src, long ld, int L, int tid) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int u = tid + i * NTHR, row = min(u >> 2, L - 1);
+      r[i] = *reinterpret_cast<const uint4*>(src + (long)row * ld + (u & 3) * 8);
+    }
+  }
+  __device__ __forceinline__ void store(unsigned char* img, int L, int tid) const {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int u = tid + i * NTHR;
+      if (u < LP * 4) *reinterpret_cast<uint4*>(img + (u >> 2) * AROW + (u & 3) * 16) = (u >> 2) < L ? r[i] : make_uint4(0, 0, 0, 0);
+    }
+  }
+};
+
 template <int NTQ, int NTK, bool AMASK>
 __global__ __launch_bounds__(256, 2) void attn_bwd_mfma_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ k,
                                                                long ldk, const bf16_t* __restrict__ v, long ldv,
@@ -148,89 +172,73 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_mfma_kernel(const bf16_t* __r
   float* Ls = reinterpret_cast<float*>(Di + LqP * AROW);   // lse   [LqP]
   float* De = Ls + LqP;                                 // delta [LqP]
   float* Kb = De + LqP;                                 // key bias [LkP]
+  unsigned char* Si = reinterpret_cast<unsigned char*>(Kb + LkP);   // dS image, bf16 [NTQ][LkP keys][32 queries], 64-B rows
+  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = blockDim.x, nwave = nthr >> 6;
-  stage_image(Qi, q + (long)b * Lq * ldq + h * AD, ldq, Lq, LqP, tid, nthr);
-  stage_image(Ki, k + (long)b * Lk * ldk + h * AD, ldk, Lk, LkP, tid, nthr);
-  stage_image(Vi, v + (long)b * Lk * ldv + h * AD, ldv, Lk, LkP, tid, nthr);
-  stage_image(Di, dout + (long)b * Lq * lddo + h * AD, lddo, Lq, LqP, tid, nthr);
-  stage_key_bias(Kb, kpm ? kpm + (long)b * Lk : nullptr, Lk, LkP, tid, nthr);
-  for (int i = tid; i < LqP; i += nthr) {
-    float dl = 0.f, l = 0.f;
-    if (i < Lq) {
-      l = lse[((long)b * H + h) * Lq + i];
-      const uint4* op = reinterpret_cast<const uint4*>(o + ((long)b * Lq + i) * ldo + h * AD);
-      const uint4* dp = reinterpret_cast<const uint4*>(dout + ((long)b * Lq + i) * lddo + h * AD);
+  // one wave per tile of the longer side (attn_bwd_mfma_try launches exactly this many threads)
+  constexpr int NTHR = 64 * (NTQ > NTK ? NTQ : NTK), nwave = NTHR / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // Prologue.  Every global load of a thread is issued before the first LDS store waits for one: the workgroups of a launch all
+  // start together (one round of two per CU), so a dependent load - store - load chain per image and loop trip is a chain of exposed
+  // memory round trips.  Here it is one.
+  const uint32_t sd = eff_seed(seed, seed_ptr);
+  BwdChunks<LqP, NTHR> cq, cd;
+  BwdChunks<LkP, NTHR> ck, cv;
+  uint4 ro[4], rg[4];                                   // row tid of o and dO: delta = dO . o
+  const int qrow = min(tid, Lq - 1);
+  const float l = lse[((long)b * H + h) * Lq + qrow];
+  {
+    const uint4* op = reinterpret_cast<const uint4*>(o + ((long)b * Lq + qrow) * ldo + h * AD);
+    const uint4* dp = reinterpret_cast<const uint4*>(dout + ((long)b * Lq + qrow) * lddo + h * AD);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { ro[c] = op[c]; rg[c] = dp[c]; }
+  }
+  cq.load(q + (long)b * Lq * ldq + h * AD, ldq, Lq, tid);
+  ck.load(k + (long)b * Lk * ldk + h * AD, ldk, Lk, tid);
+  cv.load(v + (long)b * Lk * ldv + h * AD, ldv, Lk, tid);
+  cd.load(dout + (long)b * Lq * lddo + h * AD, lddo, Lq, tid);
+  uint8_t kp = 0;
+  if (kpm) kp = kpm[(long)b * Lk + min(tid, Lk - 1)];   // the one branch, after every other load is on its way
+  cq.store(Qi, Lq, tid);
+  ck.store(Ki, Lk, tid);
+  cv.store(Vi, Lk, tid);
+  cd.store(Di, Lq, tid);
+  if (tid < LkP) Kb[tid] = (tid >= Lk || kp) ? -INFINITY : 0.f;      // LkP, LqP <= NTHR / 2
+  if (tid < LqP) {
+    float dl = 0.f;
+    if (tid < Lq) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const bf16x8 a = __builtin_bit_cast(bf16x8, op[c]), g = __builtin_bit_cast(bf16x8, dp[c]);
+        const bf16x8 a = __builtin_bit_cast(bf16x8, ro[c]), g = __builtin_bit_cast(bf16x8, rg[c]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) dl += (float)a[e] * (float)g[e];
       }
     }
-    Ls[i] = l;
-    De[i] = dl;
+    Ls[tid] = tid < Lq ? l : 0.f;
+    De[tid] = dl;
   }
   __syncthreads();
-  const uint32_t sd = eff_seed(seed, seed_ptr);
   const int hf = lane >> 5;
 
-  // ---------------- pass A: this wave's 32 queries, all keys -> dQ
-  for (int q0 = wave * 32; q0 < Lq; q0 += nwave * 32) {
-    const int qi = q0 + (lane & 31);
-    const float lq = Ls[qi], dlq = De[qi];
-    const uint64_t rowbase = ((uint64_t)bh * Lq + qi) * Lk;
-    const uint32_t d_hi = (uint32_t)(rowbase >> 33), d_inner = drop_inner(sd, d_hi);
-    f32x16 dqa;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dqa[r] = 0.f;
-#pragma unroll 1
-    for (int kt = 0; kt < NTK; ++kt) {
-      f32x16 st, dp;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { st[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 qf = frag_rows(Qi, q0, ks, lane), df = frag_rows(Di, q0, ks, lane);
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(Ki, kt * 32, ks, lane), qf, st, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(Vi, kt * 32, ks, lane), df, dp, 0, 0, 0);
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        float ds[8];
-#pragma unroll
-        for (int g2 = 0; g2 < 2; ++g2) {
-          const int key0 = kt * 32 + 16 * u + 8 * g2 + 4 * hf;
-          const float4 kb = *reinterpret_cast<const float4*>(Kb + key0);
-          const float kbv[4] = {kb.x, kb.y, kb.z, kb.w};
-          uint32_t keep = 0xfu;
-          if (thresh) keep = drop_keep4(d_inner, d_hi, sd, rowbase + key0, thresh);      // four consecutive keys: two hashes
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = 8 * u + 4 * g2 + e, key = key0 + e;
-            float sc = st[r] * scale + kbv[e];
-            if (AMASK) { if (qi < Lq && key < Lk) sc += amask[(long)qi * Lk + key]; }
-            const float p = __expf(sc - lq);
-            float g = dp[r];
-            if (thresh) g = (keep >> e & 1u) ? g * inv_keep : 0.f;
-            ds[4 * g2 + e] = (qi < Lq) ? p * (g - dlq) : 0.f;
-          }
-        }
-        dqa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8(ds), frag_cols_tr(Ki, kt * 32 + 16 * u, lane), dqa, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qr = q0 + crow(r, hf);
-      if (qr < Lq) dq[((long)b * Lq + qr) * lddq + h * AD + (lane & 31)] = (bf16_t)(dqa[r] * scale);
-    }
-  }
-
-  // ---------------- pass B: this wave's 32 keys, all queries -> dK, dV (accumulated transposed: rows = dims, cols = keys)
+  // ---------------- pass B: this wave's 32 keys, all queries -> dK, dV (accumulated transposed: rows = dims, cols = keys) and the
+  // dS image.  Every key tile belongs to one wave and every (query tile, key, query) element of the image is written (zero where
+  // the query is beyond Lq or the key is padded: p = 0 there), so the dQ phase reads nothing stale.
   for (int k0 = wave * 32; k0 < Lk; k0 += nwave * 32) {
     const int kj = k0 + (lane & 31);                    // this lane's key
     const float kbj = Kb[kj];
-    const uint32_t k_hi = (uint32_t)((((uint64_t)bh * Lq) * Lk) >> 33), k_inner = drop_inner(sd, k_hi);   // seed half of the dropout hash
+    // The dropout hash of element e0 + t0 (e0: this (clip, head)'s first element, t0 = query * Lk + key < 2^14) is that of the 64-bit
+    // index (e0 >> 1) + x, x = ((e0 & 1) + t0) >> 1.  Its high word is that of e0 >> 1 plus the carry of the low words' sum, so the
+    // seed half of the hash is one of two values computed here, and what is left per element is 32-bit arithmetic.
+    const uint64_t e0 = ((uint64_t)bh * Lq) * Lk;
+    const uint32_t k_hi = (uint32_t)(e0 >> 33), hb_lo = (uint32_t)(e0 >> 1);
+    const uint32_t k_inner = drop_inner(sd, k_hi), k_inner_c = drop_inner(sd, k_hi + 1);
+    const uint32_t tl = (uint32_t)(e0 & 1) + kj + 4 * hf * Lk;   // the lane's part of (e0 & 1) + t0
+    auto keep_at = [&](int qu) -> bool {                         // qu = query - 4 * hf: uniform
+      const uint32_t t = tl + (uint32_t)(qu * Lk);
+      const uint32_t lo = hb_lo + (t >> 1);
+      const uint32_t hs = mix32(lo ^ (lo < hb_lo ? k_inner_c : k_inner));
+      return __builtin_amdgcn_ubfe(hs, (t & 1u) << 4, 16) >= thresh;
+    };
     f32x16 dkt, dvt;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dkt[r] = 0.f; dvt[r] = 0.f; }
@@ -261,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_mfma_kernel(const bf16_t* __r
             float p = (qr < Lq) ? __expf(sc - lv[e]) : 0.f;
             float g = dp[r], pk = p;
             if (thresh) {
-              const bool keep = drop_keep_in(k_inner, k_hi, sd, ((uint64_t)bh * Lq + qr) * Lk + kj, thresh);
+              const bool keep = keep_at(qr - 4 * hf);
               g = keep ? g * inv_keep : 0.f;
               pk = keep ? p * inv_keep : 0.f;
             }
@@ -269,15 +277,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_mfma_kernel(const bf16_t* __r
             ds[4 * g2 + e] = p * (g - dv4[e]);
           }
         }
+        // the bf16 dS that feeds dK also goes to the image: a lane's four consecutive queries of one register group are 8 bytes
+        // of its key's row
+        const bf16x8 dsb = pack8(ds);
+        unsigned char* srow = Si + (long)(qt * LkP + kj) * AROW + (16 * u + 4 * hf) * 2;
+        *reinterpret_cast<bf16x4*>(srow) = __builtin_shufflevector(dsb, dsb, 0, 1, 2, 3);
+        *reinterpret_cast<bf16x4*>(srow + 16) = __builtin_shufflevector(dsb, dsb, 4, 5, 6, 7);
         dvt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_tr(Di, qt * 32 + 16 * u, lane), pack8(pd), dvt, 0, 0, 0);
-        dkt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_tr(Qi, qt * 32 + 16 * u, lane), pack8(ds), dkt, 0, 0, 0);
+        dkt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_tr(Qi, qt * 32 + 16 * u, lane), dsb, dkt, 0, 0, 0);
       }
     }
     // dvt/dkt: register r <-> dim crow(r, hf), lane <-> key: four 4-dim (8-byte) stores per row
     if (kj < Lk) {
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
         bf16x4 a, c;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { a[e] = (bf16_t)(dkt[4 * g4 + e] * scale); c[e] = (bf16_t)dvt[4 * g4 + e]; }
@@ -285,6 +298,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_mfma_kernel(const bf16_t* __r
         *reinterpret_cast<bf16x4*>(dk + ((long)b * Lk + kj) * lddk + h * AD + d0) = a;
         *reinterpret_cast<bf16x4*>(dv + ((long)b * Lk + kj) * lddv + h * AD + d0) = c;
       }
+    }
+  }
+  __syncthreads();                                      // every wave's dS stores have retired
+
+  // ---------------- dQ phase: this wave's 32 queries, all keys: dQ = dS K, both operands through transposing reads of images whose
+  // rows are keys (k-slots in the same order).  One wave sums a query row over the key tiles in ascending order.
+  for (int q0 = wave * 32; q0 < Lq; q0 += nwave * 32) {
+    const unsigned char* Sq = Si + (long)q0 * LkP * 2;  // query tile q0 / 32 of the image
+    f32x16 dqa;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dqa[r] = 0.f;
+#pragma unroll
+    for (int kb16 = 0; kb16 < LkP; kb16 += 16)
+      dqa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_tr(Sq, kb16, lane), frag_cols_tr(Ki, kb16, lane), dqa, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qr = q0 + crow(r, hf);
+      if (qr < Lq) dq[((long)b * Lq + qr) * lddq + h * AD + (lane & 31)] = (bf16_t)(dqa[r] * scale);
     }
   }
 }
@@ -391,7 +422,9 @@ int attn_bwd_mfma_try(const void* q, int64_t ldq, const void* k, int64_t ldk, co
                       float drop_p, uint32_t seed, const uint32_t* seed_ptr, hipStream_t st) {
   if (!attn_bwd_mfma_fits(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dk, lddk, dv, lddv, Lq, Lk)) return -1;
   const int ntq = (Lq + 31) / 32, ntk = (Lk + 31) / 32;
-  const size_t lds = (size_t)(2 * ntq * 32 + 2 * ntk * 32) * AROW + (size_t)(2 * ntq * 32 + ntk * 32) * sizeof(float);
+  // Q / dO and K / V images, lse / delta / key bias, the dS image (at most 32 KB; 65.5 KB in all at 4 x 4: two workgroups per CU)
+  const size_t lds = (size_t)(2 * ntq * 32 + 2 * ntk * 32) * AROW + (size_t)(2 * ntq * 32 + ntk * 32) * sizeof(float) +
+                     (size_t)(ntq * 32) * (ntk * 32) * sizeof(bf16_t);
   const int nwave = std::min(4, std::max(ntq, ntk));
   const float scale = 1.f / sqrtf((float)AD);
   const uint32_t th = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
