@@ -8,25 +8,20 @@
 #include <cmath>
 
 #include "common.h"
+#include "event_records.h"
 
 #pragma clang fp contract(off)     // offset - onset >= min_duration is the plain f32 subtract and compare of the reference
 
 namespace sedt {
 
-#define SEDT_DE_MAXQ 64            // queries per clip (one lane each)
-#define SEDT_DE_MAXC 63            // classes (the limit of event_metrics_kernel, kept so both accept the same model)
-#define SEDT_DE_MAXK 1024          // thresholds per launch (gridDim.y)
-#define SEDT_DE_SLOT 5             // words of one event record {class, onset, offset, score, query}
-
 // block = 64 threads = one wave, blockIdx.x = clip of the batch, blockIdx.y = threshold of the grid.
-//   out [K][B][1 + 5 Q] 32-bit words: {n, then Q slots of {class int32, onset f32, offset f32, score f32, query int32}}; the slots
-//   at or past n hold {-1, 0, 0, 0, -1}
+//   out [K][B][1 + 5 Q] 32-bit words: the records of event_records.h
 __global__ __launch_bounds__(64) void decode_events_kernel(const float* __restrict__ scores, const int64_t* __restrict__ labels,
                                                            const float* __restrict__ boxes, const float* __restrict__ thresholds,
                                                            int class_wise, int B, int Q, int C, float min_dur, float max_len,
                                                            int del_overlap, int32_t* __restrict__ out) {
-  __shared__ float s_on[SEDT_DE_MAXQ], s_end[SEDT_DE_MAXQ], s_score[SEDT_DE_MAXQ];
-  __shared__ int s_lab[SEDT_DE_MAXQ], s_surv[SEDT_DE_MAXQ], s_order[SEDT_DE_MAXQ];
+  __shared__ float s_on[SEDT_MAX_QUERIES], s_end[SEDT_MAX_QUERIES], s_score[SEDT_MAX_QUERIES];
+  __shared__ int s_lab[SEDT_MAX_QUERIES], s_surv[SEDT_MAX_QUERIES], s_order[SEDT_MAX_QUERIES];
   const int b = blockIdx.x, kt = blockIdx.y, lane = threadIdx.x;
   // read on every launch: a captured graph follows an edited grid.  thresholds [K] (class_wise 0: one per operating point) or [K][C]
   // (one per operating point and class, looked up by the query's label once that is known to be a class)
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(64) void decode_events_kernel(const float* __restri
   const bool surv = lane < n_kept && s_surv[q];
   const unsigned long long alive = __ballot(surv);
   const int n = __popcll(alive);
-  int32_t* rec = out + ((long)kt * B + b) * (1 + SEDT_DE_SLOT * Q);
+  int32_t* rec = record_at(out, kt, B, b, Q);
   if (lane == 0) rec[0] = n;
   if (surv) {
     float o = s_on[q], e = s_end[q];
@@ -104,16 +99,16 @@ __global__ __launch_bounds__(64) void decode_events_kernel(const float* __restri
       o = fminf(fmaxf(o, 0.f), max_len);
       e = fminf(fmaxf(e, 0.f), max_len);
     }
-    int32_t* s = rec + 1 + SEDT_DE_SLOT * __popcll(alive & ((1ull << lane) - 1ull));
-    s[0] = s_lab[q];
-    s[1] = __float_as_int(o);
-    s[2] = __float_as_int(e);
-    s[3] = __float_as_int(s_score[q]);
-    s[4] = q;
+    int32_t* s = record_slot(rec, __popcll(alive & ((1ull << lane) - 1ull)));
+    s[SEDT_REC_CLASS] = s_lab[q];
+    s[SEDT_REC_ONSET] = __float_as_int(o);
+    s[SEDT_REC_OFFSET] = __float_as_int(e);
+    s[SEDT_REC_SCORE] = __float_as_int(s_score[q]);
+    s[SEDT_REC_QUERY] = q;
   }
   if (lane >= n && lane < Q) {
-    int32_t* s = rec + 1 + SEDT_DE_SLOT * lane;
-    s[0] = -1; s[1] = 0; s[2] = 0; s[3] = 0; s[4] = -1;
+    int32_t* s = record_slot(rec, lane);
+    s[SEDT_REC_CLASS] = -1; s[SEDT_REC_ONSET] = 0; s[SEDT_REC_OFFSET] = 0; s[SEDT_REC_SCORE] = 0; s[SEDT_REC_QUERY] = -1;
   }
 }
 
@@ -125,9 +120,9 @@ int decode_events_launch(const char* what, const float* scores, const int64_t* l
                          int class_wise, int B, int Q, int C, int K, float min_duration, double max_len, int del_overlap, int32_t* out,
                          void* stream) {
   SEDT_REQUIRE(scores && labels && boxes && thresholds && out, "%s: null pointer", what);
-  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_DE_MAXQ && C >= 1 && C <= SEDT_DE_MAXC, "%s: B=%d Q=%d (<=%d) C=%d (<=%d)", what, B, Q,
-               SEDT_DE_MAXQ, C, SEDT_DE_MAXC);
-  SEDT_REQUIRE(K >= 1 && K <= SEDT_DE_MAXK, "%s: %d thresholds (1 .. %d)", what, K, SEDT_DE_MAXK);
+  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_MAX_QUERIES && C >= 1 && C <= SEDT_MAX_CLASSES, "%s: B=%d Q=%d (<=%d) C=%d (<=%d)", what, B, Q,
+               SEDT_MAX_QUERIES, C, SEDT_MAX_CLASSES);
+  SEDT_REQUIRE(K >= 1 && K <= SEDT_MAX_THRESHOLDS, "%s: %d thresholds (1 .. %d)", what, K, SEDT_MAX_THRESHOLDS);
   SEDT_REQUIRE(max_len >= 0.0 && (double)(float)max_len == max_len,
                "%s: max_len %.17g is not a non-negative number float32 represents exactly (+inf: no clip)", what, max_len);
   if (B == 0) return 0;

@@ -7,14 +7,11 @@
 // entries of its own estimates and references only, and own one row of the queue each.
 #pragma once
 #include "common.h"
+#include "event_records.h"
 
 #pragma clang fp contract(off)     // the float64 collar tests must be the plain sub / mul / compare sed_eval evaluates
 
 namespace sedt {
-
-#define SEDT_MT_MAXQ 64            // estimates per clip (one bit of a hit-graph row each)
-#define SEDT_MT_MAXC 63            // classes (one lane, one queue row each)
-#define SEDT_MT_MAXR 64            // reference events per clip (one row of the hit graph each)
 
 // every lane of the wave calls this (it votes): lane = estimate, `live` whether the lane holds one, (cls, on, end) its class and its
 // float64 times.  A hit: same class, |on_r - on_e| <= t_collar, |off_r - off_e| <= max(t_collar, pct * (off_r - on_r)).

@@ -15,9 +15,6 @@
 
 namespace sedt {
 
-#define SEDT_EM_MAXQ 64            // queries per clip (one lane each)
-#define SEDT_EM_MAXC 63            // classes (one lane each in the per-class passes)
-#define SEDT_EM_MAXR 64            // reference events per clip (one bit row of the hit graph each)
 #define SEDT_EM_MAXSEG 1024        // segments per clip of the segment-based counts (10 s at 10 ms)
 #define SEDT_EM_SEGW (SEDT_EM_MAXSEG / 64)   // 64-bit words of one class's segment row
 
@@ -52,20 +49,20 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
                                                            double pct, int del_overlap, int optimal, unsigned long long* __restrict__ ev,
                                                            unsigned long long* __restrict__ tag, double seg_res, int seg_words,
                                                            unsigned long long* __restrict__ seg, unsigned long long* __restrict__ sdi) {
-  __shared__ float s_on[SEDT_EM_MAXQ], s_end[SEDT_EM_MAXQ], s_score[SEDT_EM_MAXQ];
-  __shared__ int s_lab[SEDT_EM_MAXQ], s_keep[SEDT_EM_MAXQ], s_surv[SEDT_EM_MAXQ], s_order[SEDT_EM_MAXQ];
-  __shared__ int r_cls[SEDT_EM_MAXR];
-  __shared__ double r_on[SEDT_EM_MAXR], r_end[SEDT_EM_MAXR];
-  __shared__ unsigned long long adj[SEDT_EM_MAXR];                  // adj[j] bit q: estimate q hits reference j
-  __shared__ int match_est[SEDT_EM_MAXQ], from_ref[SEDT_EM_MAXQ], match_ref[SEDT_EM_MAXR];
-  __shared__ unsigned char queue[SEDT_EM_MAXC][SEDT_EM_MAXR];       // BFS queue of class c (refs of one class, one clip)
+  __shared__ float s_on[SEDT_MAX_QUERIES], s_end[SEDT_MAX_QUERIES], s_score[SEDT_MAX_QUERIES];
+  __shared__ int s_lab[SEDT_MAX_QUERIES], s_keep[SEDT_MAX_QUERIES], s_surv[SEDT_MAX_QUERIES], s_order[SEDT_MAX_QUERIES];
+  __shared__ int r_cls[SEDT_MAX_REF_EVENTS];
+  __shared__ double r_on[SEDT_MAX_REF_EVENTS], r_end[SEDT_MAX_REF_EVENTS];
+  __shared__ unsigned long long adj[SEDT_MAX_REF_EVENTS];                  // adj[j] bit q: estimate q hits reference j
+  __shared__ int match_est[SEDT_MAX_QUERIES], from_ref[SEDT_MAX_QUERIES], match_ref[SEDT_MAX_REF_EVENTS];
+  __shared__ unsigned char queue[SEDT_MAX_CLASSES][SEDT_MAX_REF_EVENTS];       // BFS queue of class c (refs of one class, one clip)
   const int b = blockIdx.x, lane = threadIdx.x;
   int clip = clip_idx[b];
   if (clip >= n_clips || (clip >= 0 && ref_present && !ref_present[clip])) clip = -1;   // not in the reference (the host validates)
   int e0 = 0, ne = 0;
   if (clip >= 0) {
     e0 = ref_off[clip];
-    ne = min(ref_off[clip + 1] - e0, SEDT_EM_MAXR);                  // sedt_event_metrics_update checks the table on the host
+    ne = min(ref_off[clip + 1] - e0, SEDT_MAX_REF_EVENTS);                  // sedt_event_metrics_update checks the table on the host
   }
 
   // ---- decode_strong: keep, then order by (class, onset, query) with del_overlap / (class, query) without
@@ -88,7 +85,7 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
     const bool before = lj < lab || (lj == lab && (del_overlap ? (oj < on || (oj == on && j < lane)) : j < lane));
     pos += (kj && before) ? 1 : 0;
   }
-  if (lane < SEDT_EM_MAXQ) {
+  if (lane < SEDT_MAX_QUERIES) {
     s_on[lane] = on; s_end[lane] = end; s_score[lane] = sc; s_lab[lane] = lab;
     s_keep[lane] = keep; s_surv[lane] = keep;
     match_est[lane] = -1;
@@ -142,25 +139,10 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
   if (c < C) {
     for (int k = 0; k < n_c; ++k) n_sys += s_surv[s_order[start + k]];
     tp = event_class_match(c, ne, r_cls, adj, match_est, from_ref, match_ref, queue[c], optimal, s_order + start, n_c, n_ref);
-    if (clip >= 0) {
-      unsigned long long* e = ev + ((long)fusion * C + c) * 3;
-      if (tp) atomicAdd(e, (unsigned long long)tp);
-      if (n_ref) atomicAdd(e + 1, (unsigned long long)n_ref);
-      if (n_sys) atomicAdd(e + 2, (unsigned long long)n_sys);
-    }
+    if (clip >= 0) add_counts3(ev + ((long)fusion * C + c) * 3, tp, n_ref, n_sys);
     // ---- clip level: class present among the decoded events / among the reference events / among the audio tags
-    const bool ref_has = n_ref > 0, sys_has = n_sys > 0;
-    unsigned long long* t = tag + ((long)fusion * C + c) * 3;
-    if (ref_has && sys_has) atomicAdd(t, 1ull);
-    if (!ref_has && sys_has) atomicAdd(t + 1, 1ull);
-    if (ref_has && !sys_has) atomicAdd(t + 2, 1ull);
-    if (at_tags) {
-      const bool at_has = at_tags[(long)b * C + c] != 0;
-      unsigned long long* a = tag + ((long)n_fusion * C + c) * 3;
-      if (ref_has && at_has) atomicAdd(a, 1ull);
-      if (!ref_has && at_has) atomicAdd(a + 1, 1ull);
-      if (ref_has && !at_has) atomicAdd(a + 2, 1ull);
-    }
+    add_presence(tag + ((long)fusion * C + c) * 3, n_ref > 0, n_sys > 0);
+    if (at_tags) add_presence(tag + ((long)n_fusion * C + c) * 3, n_ref > 0, at_tags[(long)b * C + c] != 0);
   }
 
   // ---- segment-based counts (sed_eval SegmentBasedMetrics): the clipped survivors (the values the hit test used) and the clip's
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
   // true negatives, which are not counted
   if constexpr (SEG) {
     if (clip < 0) return;                                          // block-uniform: only reference clips are evaluated
-    __shared__ unsigned long long roll_ref[SEDT_EM_MAXC * SEDT_EM_SEGW], roll_sys[SEDT_EM_MAXC * SEDT_EM_SEGW];
+    __shared__ unsigned long long roll_ref[SEDT_MAX_CLASSES * SEDT_EM_SEGW], roll_sys[SEDT_MAX_CLASSES * SEDT_EM_SEGW];
     const int W = seg_words;
     for (int i = lane; i < C * W; i += 64) {
       roll_ref[i] = 0ull;
@@ -187,10 +169,7 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
         s_ref += __popcll(a);
         s_sys += __popcll(s);
       }
-      unsigned long long* e = seg + ((long)fusion * C + c) * 3;
-      if (s_tp) atomicAdd(e, (unsigned long long)s_tp);
-      if (s_ref) atomicAdd(e + 1, (unsigned long long)s_ref);
-      if (s_sys) atomicAdd(e + 2, (unsigned long long)s_sys);
+      add_counts3(seg + ((long)fusion * C + c) * 3, s_tp, s_ref, s_sys);
     }
     // per segment (lane = bit of the word), over the classes active anywhere in the clip (the others add nothing):
     // S += min(Nref, Nsys) - Ntp, D += max(0, Nref - Nsys), I += max(0, Nsys - Nref)
@@ -214,12 +193,7 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const float* __restri
       n_del += __shfl_xor(n_del, o, 64);
       n_ins += __shfl_xor(n_ins, o, 64);
     }
-    if (lane == 0) {
-      unsigned long long* t = sdi + (long)fusion * 3;
-      if (n_sub) atomicAdd(t, (unsigned long long)n_sub);
-      if (n_del) atomicAdd(t + 1, (unsigned long long)n_del);
-      if (n_ins) atomicAdd(t + 2, (unsigned long long)n_ins);
-    }
+    if (lane == 0) add_counts3(sdi + (long)fusion * 3, n_sub, n_del, n_ins);
   }
 }
 
@@ -231,12 +205,8 @@ int event_metrics_launch(const char* what, const float* scores, const int64_t* l
                          int optimal, int64_t* ev_counts, int64_t* tag_counts, double seg_res, int seg_words, int64_t* seg_counts,
                          int64_t* sdi_counts, void* stream) {
   SEDT_REQUIRE(scores && labels && boxes && clip_idx && ref_off && ev_counts && tag_counts, "event_metrics_update: null pointer");
-  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_EM_MAXQ && C >= 1 && C <= SEDT_EM_MAXC, "event_metrics_update: B=%d Q=%d (<=%d) C=%d (<=%d)",
-               B, Q, SEDT_EM_MAXQ, C, SEDT_EM_MAXC);
-  SEDT_REQUIRE(n_clips >= 0 && (n_clips == 0 || (ref_cls && ref_on && ref_end)), "event_metrics_update: reference table missing");
-  SEDT_REQUIRE(max_ref >= 0 && max_ref <= SEDT_EM_MAXR, "event_metrics_update: a clip has %d reference events (<= %d)", max_ref,
-               SEDT_EM_MAXR);
-  SEDT_REQUIRE(n_fusion >= 1 && fusion >= 0 && fusion < n_fusion, "event_metrics_update: fusion %d of %d", fusion, n_fusion);
+  // one threshold: K = 1
+  if (clip_args_ok("event_metrics_update", B, Q, C, 1, n_clips, ref_cls && ref_on && ref_end, max_ref, n_fusion, fusion)) return 1;
   if (B == 0) return 0;
   hipLaunchKernelGGL(event_metrics_kernel<SEG>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), scores, labels, boxes,
                      at_tags, clip_idx, ref_present, ref_off, ref_cls, ref_on, ref_end, n_clips, Q, C, n_fusion, fusion, threshold,

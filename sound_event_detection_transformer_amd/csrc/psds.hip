@@ -7,16 +7,11 @@
 // order, detections in record order), so a sum that lands exactly on a threshold does so here and on the host alike.  Counts land in
 // int64 counters through integer atomics only: a replay is bit-reproducible and independent of the order the clips arrive in.
 #include "common.h"
+#include "event_records.h"
 
 #pragma clang fp contract(off)     // inter / dur added to a running sum: no fused multiply-add may stand in for the division's tail
 
 namespace sedt {
-
-#define SEDT_PS_MAXQ 64            // event slots of a record (one lane each in phase 1)
-#define SEDT_PS_MAXC 63            // classes (decode_events_kernel's limit)
-#define SEDT_PS_MAXK 1024          // thresholds per launch (gridDim.y)
-#define SEDT_PS_MAXR 64            // reference events per clip (one lane each in phase 2)
-#define SEDT_PS_SLOT 5             // words of one event record {class, onset, offset, score, query}
 
 // the part of detection [on, off] inside reference event j, as a fraction of `dur`, added to `sum` when it is positive
 __device__ inline double add_overlap(double sum, double on, double off, double r_on, double r_end, double dur) {
@@ -32,16 +27,16 @@ __global__ __launch_bounds__(64) void psds_update_kernel(const int32_t* __restri
                                                          const double* __restrict__ ref_end, const double* __restrict__ ref_dur,
                                                          int n_clips, int B, int Q, int C, double dtc, double gtc, double cttc,
                                                          unsigned long long* __restrict__ counts) {
-  __shared__ int r_cls[SEDT_PS_MAXR], d_cls[SEDT_PS_MAXQ];            // -1: takes part in nothing / did not pass the DTC
-  __shared__ double r_on[SEDT_PS_MAXR], r_end[SEDT_PS_MAXR], d_on[SEDT_PS_MAXQ], d_end[SEDT_PS_MAXQ];
+  __shared__ int r_cls[SEDT_MAX_REF_EVENTS], d_cls[SEDT_MAX_QUERIES];            // -1: takes part in nothing / did not pass the DTC
+  __shared__ double r_on[SEDT_MAX_REF_EVENTS], r_end[SEDT_MAX_REF_EVENTS], d_on[SEDT_MAX_QUERIES], d_end[SEDT_MAX_QUERIES];
   const int b = blockIdx.x, kt = blockIdx.y, lane = threadIdx.x;
   const int clip = clip_idx[b];
   if (clip < 0 || clip >= n_clips || (ref_present && !ref_present[clip])) return;      // outside the table: block-uniform
-  const int32_t* rec = records + ((long)kt * B + b) * (1 + SEDT_PS_SLOT * Q);
+  const int32_t* rec = record_at(records, kt, B, b, Q);
   const int n = rec[0];
   if (n < 0 || n > Q) return;                                           // not a count decode_events writes: block-uniform
   const int e0 = ref_off[clip];
-  const int ne = min(max(ref_off[clip + 1] - e0, 0), SEDT_PS_MAXR);     // sedt_psds_update bounds max_ref on the host
+  const int ne = min(max(ref_off[clip + 1] - e0, 0), SEDT_MAX_REF_EVENTS);     // sedt_psds_update bounds max_ref on the host
   const double clip_len = ref_dur[clip];
   unsigned long long* row0 = counts + (long)kt * C * (C + 1);
 
@@ -67,10 +62,10 @@ __global__ __launch_bounds__(64) void psds_update_kernel(const int32_t* __restri
   int cls = -1;
   double on = 0.0, off = 0.0, dur = 0.0;
   if (lane < n) {
-    const int32_t* s = rec + 1 + SEDT_PS_SLOT * lane;
-    cls = s[0];
-    on = (double)__int_as_float(s[1]);
-    off = (double)__int_as_float(s[2]);
+    const int32_t* s = record_slot(rec, lane);
+    cls = s[SEDT_REC_CLASS];
+    on = (double)__int_as_float(s[SEDT_REC_ONSET]);
+    off = (double)__int_as_float(s[SEDT_REC_OFFSET]);
     dur = off - on;
     if (cls < 0 || cls >= C || !(dur > 0.0)) cls = -1;                  // never an index
   }
@@ -115,12 +110,7 @@ extern "C" int sedt_psds_update(const int32_t* records, const int32_t* clip_idx,
                                 int max_ref, int B, int Q, int C, int K, int n_fusion, int fusion, double dtc, double gtc, double cttc,
                                 int64_t* counts, void* stream) {
   using namespace sedt;
-  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_PS_MAXQ && C >= 1 && C <= SEDT_PS_MAXC, "psds_update: B=%d Q=%d (<=%d) C=%d (<=%d)", B, Q,
-               SEDT_PS_MAXQ, C, SEDT_PS_MAXC);
-  SEDT_REQUIRE(K >= 1 && K <= SEDT_PS_MAXK, "psds_update: %d thresholds (1 .. %d)", K, SEDT_PS_MAXK);
-  SEDT_REQUIRE(n_clips >= 0 && (n_clips == 0 || (ref_cls && ref_on && ref_end && ref_dur)), "psds_update: reference table missing");
-  SEDT_REQUIRE(max_ref >= 0 && max_ref <= SEDT_PS_MAXR, "psds_update: a clip has %d reference events (<= %d)", max_ref, SEDT_PS_MAXR);
-  SEDT_REQUIRE(n_fusion >= 1 && fusion >= 0 && fusion < n_fusion, "psds_update: fusion %d of %d", fusion, n_fusion);
+  if (clip_args_ok("psds_update", B, Q, C, K, n_clips, ref_cls && ref_on && ref_end && ref_dur, max_ref, n_fusion, fusion)) return 1;
   SEDT_REQUIRE(dtc == dtc && gtc == gtc && cttc == cttc, "psds_update: a tolerance criterion is NaN (dtc %g gtc %g cttc %g)", dtc, gtc, cttc);
   if (B == 0) return 0;
   SEDT_REQUIRE(records && clip_idx && ref_off && counts, "psds_update: null pointer");

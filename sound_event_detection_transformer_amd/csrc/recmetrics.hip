@@ -54,12 +54,12 @@ __global__ __launch_bounds__(64) void recording_event_counts_kernel(const int32_
                                                                     int N, int E, int R, int C, int cap, double t_collar, double pct,
                                                                     int optimal, unsigned long long* __restrict__ ev,
                                                                     unsigned long long* __restrict__ tag, int32_t* __restrict__ status) {
-  __shared__ double e_on[SEDT_MT_MAXQ + 1], e_end[SEDT_MT_MAXQ];      // the next 64 estimates and the onset of the one behind them
-  __shared__ double r_on[SEDT_MT_MAXR + 1], r_end[SEDT_MT_MAXR];      // the next 64 references and the onset of the one behind them
-  __shared__ int r_cls[SEDT_MT_MAXR];
-  __shared__ unsigned long long adj[SEDT_MT_MAXR];
-  __shared__ int match_est[SEDT_MT_MAXQ], from_ref[SEDT_MT_MAXQ], match_ref[SEDT_MT_MAXR];
-  __shared__ unsigned char queue[SEDT_MT_MAXR];
+  __shared__ double e_on[SEDT_MAX_QUERIES + 1], e_end[SEDT_MAX_QUERIES];      // the next 64 estimates and the onset of the one behind them
+  __shared__ double r_on[SEDT_MAX_REF_EVENTS + 1], r_end[SEDT_MAX_REF_EVENTS];      // the next 64 references and the onset of the one behind them
+  __shared__ int r_cls[SEDT_MAX_REF_EVENTS];
+  __shared__ unsigned long long adj[SEDT_MAX_REF_EVENTS];
+  __shared__ int match_est[SEDT_MAX_QUERIES], from_ref[SEDT_MAX_QUERIES], match_ref[SEDT_MAX_REF_EVENTS];
+  __shared__ unsigned char queue[SEDT_MAX_REF_EVENTS];
 
   const int r = blockIdx.x / C, c = blockIdx.x % C, kt = blockIdx.y, lane = threadIdx.x;
   const int ri = rec_idx[r];
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(64) void recording_event_counts_kernel(const int32_
     return;
   }
   const int n_est = min(max(cnt[c], 0), cap);
-  const double* est = reinterpret_cast<const double*>(out + (kr * C + c) * (long)cap * SEDT_RM_WORDS);
+  const double* est = reinterpret_cast<const double*>(out + (kr * C + c) * (long)cap * SEDT_EVENT_WORDS);
   int j0, j1;
   rm_ref_range(ref_off, ri, C, c, E, j0, j1);
   if (!rm_lists_ok(est, n_est, ref_on, ref_end, j0, j1, lane)) {
@@ -84,15 +84,15 @@ __global__ __launch_bounds__(64) void recording_event_counts_kernel(const int32_
   int ie = 0, ir = j0, st = 0;
   while (ie < n_est && ir < j1) {                                     // a list at its end: what is left of the other matches nothing
     // ---- stage the next 65 onsets of both lists
-    const int we = min(n_est - ie, SEDT_MT_MAXQ + 1), wr = min(j1 - ir, SEDT_MT_MAXR + 1);
+    const int we = min(n_est - ie, SEDT_MAX_QUERIES + 1), wr = min(j1 - ir, SEDT_MAX_REF_EVENTS + 1);
     __syncthreads();
     for (int i = lane; i < we; i += 64) {
-      e_on[i] = est[4 * (long)(ie + i)];
-      if (i < SEDT_MT_MAXQ) e_end[i] = est[4 * (long)(ie + i) + 1];
+      e_on[i] = est[SEDT_EVENT_DOUBLES * (long)(ie + i)];
+      if (i < SEDT_MAX_QUERIES) e_end[i] = est[SEDT_EVENT_DOUBLES * (long)(ie + i) + 1];
     }
     for (int i = lane; i < wr; i += 64) {
       r_on[i] = ref_on[ir + i];
-      if (i < SEDT_MT_MAXR) r_end[i] = ref_end[ir + i];
+      if (i < SEDT_MAX_REF_EVENTS) r_end[i] = ref_end[ir + i];
     }
     match_est[lane] = -1;
     match_ref[lane] = -1;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(64) void recording_event_counts_kernel(const int32_
       const bool take_e = he && (!hr || oe <= orf);
       const double x = take_e ? oe : orf;
       if (a + b > 0 && (x - last) > t_collar) break;
-      if ((take_e ? a : b) == SEDT_MT_MAXQ) { st = SEDT_RM_BLOCK; break; }   // a 65th estimate or reference inside one block
+      if ((take_e ? a : b) == SEDT_MAX_QUERIES) { st = SEDT_RM_BLOCK; break; }   // a 65th estimate or reference inside one block
       a += take_e ? 1 : 0;
       b += take_e ? 0 : 1;
       last = x;
@@ -132,13 +132,8 @@ __global__ __launch_bounds__(64) void recording_event_counts_kernel(const int32_
   if (lane == 0) {
     const long n_ref = j1 - j0, n_sys = n_est;
     const long cell = ((long)kt * C + c) * 3;
-    if (tp) atomicAdd(ev + cell, (unsigned long long)tp);
-    if (n_ref) atomicAdd(ev + cell + 1, (unsigned long long)n_ref);
-    if (n_sys) atomicAdd(ev + cell + 2, (unsigned long long)n_sys);
-    const bool ref_has = n_ref > 0, sys_has = cnt[c] > 0;
-    if (ref_has && sys_has) atomicAdd(tag + cell, 1ull);
-    if (!ref_has && sys_has) atomicAdd(tag + cell + 1, 1ull);
-    if (ref_has && !sys_has) atomicAdd(tag + cell + 2, 1ull);
+    add_counts3(ev + cell, tp, n_ref, n_sys);
+    add_presence(tag + cell, n_ref > 0, cnt[c] > 0);
   }
 }
 
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(64) void recording_segment_counts_kernel(const int3
   for (int c = 0; c < C && !st; ++c) {                                // the premise of the cursors, checked by the whole wave
     int j0, j1;
     rm_ref_range(ref_off, ri, C, c, E, j0, j1);
-    const double* est = reinterpret_cast<const double*>(out + (kr * C + c) * (long)cap * SEDT_RM_WORDS);
+    const double* est = reinterpret_cast<const double*>(out + (kr * C + c) * (long)cap * SEDT_EVENT_WORDS);
     if (!rm_lists_ok(est, min(max(cnt[c], 0), cap), ref_on, ref_end, j0, j1, lane)) st = SEDT_RM_UNORDERED;
   }
   if (st) {
@@ -209,11 +204,11 @@ __global__ __launch_bounds__(64) void recording_segment_counts_kernel(const int3
     return;
   }
   const int nw = min(max(n_words[r], 0), SEDT_RM_MAXWORDS), S = nw * 64;
-  RmCursor ue = {nullptr, nullptr, 4, 0, 0, 0}, ur = {nullptr, nullptr, 1, 0, 0, 0};
+  RmCursor ue = {nullptr, nullptr, SEDT_EVENT_DOUBLES, 0, 0, 0}, ur = {nullptr, nullptr, 1, 0, 0, 0};
   if (lane < C) {
     int j0, j1;
     rm_ref_range(ref_off, ri, C, lane, E, j0, j1);
-    const double* est = reinterpret_cast<const double*>(out + (kr * C + lane) * (long)cap * SEDT_RM_WORDS);
+    const double* est = reinterpret_cast<const double*>(out + (kr * C + lane) * (long)cap * SEDT_EVENT_WORDS);
     ue.on = est; ue.end = est + 1; ue.n = min(max(cnt[lane], 0), cap);
     ur.on = ref_on + j0; ur.end = ref_end + j0; ur.n = j1 - j0;
   }
@@ -254,17 +249,9 @@ __global__ __launch_bounds__(64) void recording_segment_counts_kernel(const int3
     n_d += __shfl_xor(n_d, o, 64);
     n_i += __shfl_xor(n_i, o, 64);
   }
-  if (lane < C) {
-    unsigned long long* cell = seg + ((long)kt * C + lane) * 3;
-    if (c_tp) atomicAdd(cell, (unsigned long long)c_tp);
-    if (c_ref) atomicAdd(cell + 1, (unsigned long long)c_ref);
-    if (c_sys) atomicAdd(cell + 2, (unsigned long long)c_sys);
-  }
+  if (lane < C) add_counts3(seg + ((long)kt * C + lane) * 3, c_tp, c_ref, c_sys);
   if (lane == 0) {
-    unsigned long long* cell = sdi + (long)kt * 3;
-    if (n_s) atomicAdd(cell, (unsigned long long)n_s);
-    if (n_d) atomicAdd(cell + 1, (unsigned long long)n_d);
-    if (n_i) atomicAdd(cell + 2, (unsigned long long)n_i);
+    add_counts3(sdi + (long)kt * 3, n_s, n_d, n_i);
     status[kr] = 0;
   }
 }

@@ -5,12 +5,9 @@
 #include <cmath>
 
 #include "common.h"
+#include "event_records.h"
 
 namespace sedt {
-
-#define SEDT_RM_MAXC 63            // classes (one lane each in the segment sweep)
-#define SEDT_RM_MAXK 1024          // thresholds per launch (gridDim.y)
-#define SEDT_RM_WORDS 8            // words of one stitched event (SEDT_ST_WORDS)
 
 #define SEDT_RM_INCOMPLETE 1
 #define SEDT_RM_BLOCK 2
@@ -30,15 +27,16 @@ __device__ __forceinline__ void rm_ref_range(const int32_t* ref_off, int ri, int
   j1 = min(max(ref_off[(long)ri * C + c + 1], j0), E);
 }
 
-// every lane of the wave: true when the n events at `ev` (stride 4 doubles: onset, offset) / the references j0 .. j1 are finite and
+// every lane of the wave: true when the n events at `ev` (stitched events read as doubles: onset, offset) / the references j0 .. j1 are finite and
 // ascending by onset; with `disjoint` the events may not overlap either (no onset before the previous offset)
 __device__ __forceinline__ bool rm_lists_ok(const double* ev, int n, const double* ref_on, const double* ref_end, int j0, int j1, int lane,
                                             bool disjoint = false) {
   bool bad = false;
   for (int i = lane; i < n; i += 64) {
-    const double on = ev[4 * (long)i], off = ev[4 * (long)i + 1];
-    bad = bad || !rm_finite(on) || !rm_finite(off) || (i > 0 && !(on >= ev[4 * (long)(i - 1)]));
-    if (disjoint) bad = bad || (i > 0 && !(on >= ev[4 * (long)(i - 1) + 1]));
+    const double* e = ev + SEDT_EVENT_DOUBLES * (long)i;                    // e[-SEDT_EVENT_DOUBLES ..]: the event before it
+    const double on = e[0], off = e[1];
+    bad = bad || !rm_finite(on) || !rm_finite(off) || (i > 0 && !(on >= e[-SEDT_EVENT_DOUBLES]));
+    if (disjoint) bad = bad || (i > 0 && !(on >= e[1 - SEDT_EVENT_DOUBLES]));
   }
   for (int j = j0 + lane; j < j1; j += 64) {
     const double on = ref_on[j];
@@ -50,8 +48,8 @@ __device__ __forceinline__ bool rm_lists_ok(const double* ev, int n, const doubl
 static inline int recording_args_ok(const char* what, const void* count, const void* out, const void* stitch_status, const void* rec_idx,
                                     const void* ref_off, const void* ref_on, const void* ref_end, int n_ref_rec, int n_ref_events, int K,
                                     int R, int C, int cap, int n_fusion, int fusion, const void* status) {
-  SEDT_REQUIRE(C >= 1 && C <= SEDT_RM_MAXC, "%s: C=%d (1 .. %d)", what, C, SEDT_RM_MAXC);
-  SEDT_REQUIRE(K >= 1 && K <= SEDT_RM_MAXK, "%s: %d thresholds (1 .. %d)", what, K, SEDT_RM_MAXK);
+  SEDT_REQUIRE(C >= 1 && C <= SEDT_MAX_CLASSES, "%s: C=%d (1 .. %d)", what, C, SEDT_MAX_CLASSES);
+  SEDT_REQUIRE(K >= 1 && K <= SEDT_MAX_THRESHOLDS, "%s: %d thresholds (1 .. %d)", what, K, SEDT_MAX_THRESHOLDS);
   SEDT_REQUIRE(R >= 0 && cap >= 1, "%s: R=%d (>= 0) cap=%d (>= 1)", what, R, cap);
   SEDT_REQUIRE((double)R * C <= 2147483647.0, "%s: R=%d x C=%d waves per threshold exceed the grid", what, R, C);
   SEDT_REQUIRE(n_ref_rec >= 0 && n_ref_events >= 0, "%s: reference table of %d recordings, %d events", what, n_ref_rec, n_ref_events);

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(64) void recording_psds_counts_kernel(const int32_t
     return;
   }
   const int n_det = min(max(cnt[c], 0), cap);
-  const double* det = reinterpret_cast<const double*>(out + (kr * C + c) * (long)cap * SEDT_RM_WORDS);
+  const double* det = reinterpret_cast<const double*>(out + (kr * C + c) * (long)cap * SEDT_EVENT_WORDS);
   int j0, j1;
   rm_ref_range(ref_off, ri, C, c, E, j0, j1);
   if (!rm_lists_ok(det, n_det, ref_on, ref_end, j0, j1, lane, true)) {
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(64) void recording_psds_counts_kernel(const int32_t
     const int i = base + lane;
     double on = 0.0, off = 0.0;
     if (i < n_det) {
-      on = det[4 * (long)i];
-      off = det[4 * (long)i + 1];
+      on = det[SEDT_EVENT_DOUBLES * (long)i];
+      off = det[SEDT_EVENT_DOUBLES * (long)i + 1];
     }
     const double dur = off - on;
     const bool live = i < n_det && dur > 0.0;                         // a zero-length detection takes part in nothing
@@ -135,15 +135,15 @@ __global__ __launch_bounds__(64) void recording_psds_counts_kernel(const int32_t
         int lo = 0, hi = n_det;                                       // the first d with max(on_d, off_d) > on_g
         while (lo < hi) {
           const int mid = lo + ((hi - lo) >> 1);
-          if (fmax(det[4 * (long)mid], det[4 * (long)mid + 1]) > g_on) hi = mid; else lo = mid + 1;
+          if (fmax(det[SEDT_EVENT_DOUBLES * (long)mid], det[SEDT_EVENT_DOUBLES * (long)mid + 1]) > g_on) hi = mid; else lo = mid + 1;
         }
         double v = 0.0;
         for (int i = lo; i < n_det; ++i) {
-          const double on = det[4 * (long)i];
+          const double on = det[SEDT_EVENT_DOUBLES * (long)i];
           if (!(on < g_end)) break;                                   // ascending by onset: nothing behind it overlaps g
           const unsigned long long word = __hip_atomic_load(my_pass + (i >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (!((word >> (i & 63)) & 1ull)) continue;
-          const double inter = fmin(det[4 * (long)i + 1], g_end) - fmax(on, g_on);
+          const double inter = fmin(det[SEDT_EVENT_DOUBLES * (long)i + 1], g_end) - fmax(on, g_on);
           if (inter > 0.0) v = v + inter / g_dur;
         }
         hit = v >= gtc;

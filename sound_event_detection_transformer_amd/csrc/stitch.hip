@@ -12,17 +12,13 @@
 #include <cmath>
 
 #include "common.h"
+#include "event_records.h"
 
 #pragma clang fp contract(off)     // t_w + on32, off + merge_gap: the plain float64 add and compare of the definition
 
 namespace sedt {
 
-#define SEDT_ST_MAXQ 64            // queries per window (decode_events_kernel's limit: one lane each)
-#define SEDT_ST_MAXC 63            // classes (decode_events_kernel's limit)
-#define SEDT_ST_MAXK 1024          // thresholds per launch (gridDim.y)
-#define SEDT_ST_SLOT 5             // words of one decode record slot {class, onset, offset, score, query}
 #define SEDT_ST_OPEN 640           // open merged events + the candidates of the window being added: (8 + 1) * 64 and a chunk to spare
-#define SEDT_ST_WORDS 8            // words of one output event {onset f64, offset f64, score f32, n_merged, window, query}
 
 #define SEDT_ST_UNORDERED 1        // status bits: win_start of the recording not ascending (or NaN)
 #define SEDT_ST_OVERFLOW 2         //   more than SEDT_ST_OPEN open events + candidates at some window
@@ -48,16 +44,16 @@ __global__ __launch_bounds__(64) void stitch_events_kernel(const int32_t* __rest
   __shared__ float o_score[SEDT_ST_OPEN];
   __shared__ int o_n[SEDT_ST_OPEN], o_win[SEDT_ST_OPEN], o_q[SEDT_ST_OPEN], o_slot[SEDT_ST_OPEN], o_cls[SEDT_ST_OPEN], o_fin[SEDT_ST_OPEN];
   // the kept candidates of the window being added, in slot order
-  __shared__ double c_on[SEDT_ST_MAXQ], c_off[SEDT_ST_MAXQ];
-  __shared__ float c_score[SEDT_ST_MAXQ];
-  __shared__ int c_cls[SEDT_ST_MAXQ], c_q[SEDT_ST_MAXQ], c_slot[SEDT_ST_MAXQ];
-  __shared__ int s_cnt[SEDT_ST_MAXC + 1];
+  __shared__ double c_on[SEDT_MAX_QUERIES], c_off[SEDT_MAX_QUERIES];
+  __shared__ float c_score[SEDT_MAX_QUERIES];
+  __shared__ int c_cls[SEDT_MAX_QUERIES], c_q[SEDT_MAX_QUERIES], c_slot[SEDT_MAX_QUERIES];
+  __shared__ int s_cnt[SEDT_MAX_CLASSES + 1];
 
   const int r = blockIdx.x, kt = blockIdx.y, lane = threadIdx.x;
   const unsigned long long lt = (1ull << lane) - 1ull;
   int32_t* cnt_out = count + ((long)kt * R + r) * C;
-  int32_t* out_r = out + ((long)kt * R + r) * C * (long)cap * SEDT_ST_WORDS;
-  if (lane <= SEDT_ST_MAXC) s_cnt[lane] = 0;
+  int32_t* out_r = out + ((long)kt * R + r) * C * (long)cap * SEDT_EVENT_WORDS;
+  if (lane <= SEDT_MAX_CLASSES) s_cnt[lane] = 0;
   const int w0 = win_off[r], w1 = win_off[r + 1];
   int st = 0;
   if (w0 < 0 || w1 < w0 || w1 > W) st = SEDT_ST_TABLE;
@@ -80,20 +76,20 @@ __global__ __launch_bounds__(64) void stitch_events_kernel(const int32_t* __rest
     // ---- the window's kept candidates (one lane per slot)
     int n_kept = 0;
     if (!flush) {
-      const int32_t* rec = records + ((long)kt * W_stride + w) * (1 + SEDT_ST_SLOT * Q);
+      const int32_t* rec = record_at(records, kt, W_stride, w, Q);
       const int n_w = rec[0];
       bool kept = false;
       double on = 0.0, off = 0.0;
       float sc = 0.f;
       int cls = -1, q = -1;
       if (n_w >= 0 && n_w <= Q && lane < n_w) {                         // a count outside 0 .. Q: the record is skipped whole
-        const int32_t* s = rec + 1 + SEDT_ST_SLOT * lane;
-        cls = s[0];
-        const double a = tw + (double)__int_as_float(s[1]), b = tw + (double)__int_as_float(s[2]);
+        const int32_t* s = record_slot(rec, lane);
+        cls = s[SEDT_REC_CLASS];
+        const double a = tw + (double)__int_as_float(s[SEDT_REC_ONSET]), b = tw + (double)__int_as_float(s[SEDT_REC_OFFSET]);
         on = a > dur ? dur : a;                                         // min(., rec_dur); a NaN stays one and fails the compare below
         off = b > dur ? dur : b;
-        sc = __int_as_float(s[3]);
-        q = s[4];
+        sc = __int_as_float(s[SEDT_REC_SCORE]);
+        q = s[SEDT_REC_QUERY];
         kept = cls >= 0 && cls < C && (off - on) > 0.0 && sc == sc;
       }
       if (__ballot(kept && on < tw)) { st = SEDT_ST_EARLY; break; }
@@ -117,13 +113,13 @@ __global__ __launch_bounds__(64) void stitch_events_kernel(const int32_t* __rest
       for (int j = 0; j < N; ++j) rank += (o_fin[j] && o_cls[j] == cls && o_on[j] < on) ? 1 : 0;
       const long pos = (long)s_cnt[cls] + rank;
       if (pos < cap) {
-        int32_t* e = out_r + ((long)cls * cap + pos) * SEDT_ST_WORDS;
+        int32_t* e = out_r + ((long)cls * cap + pos) * SEDT_EVENT_WORDS;
         reinterpret_cast<double*>(e)[0] = on;
         reinterpret_cast<double*>(e)[1] = o_off[i];
-        e[4] = __float_as_int(o_score[i]);
-        e[5] = o_n[i];
-        e[6] = o_win[i];
-        e[7] = o_q[i];
+        e[SEDT_EVENT_SCORE] = __float_as_int(o_score[i]);
+        e[SEDT_EVENT_MERGED] = o_n[i];
+        e[SEDT_EVENT_WINDOW] = o_win[i];
+        e[SEDT_EVENT_QUERY] = o_q[i];
       }
     }
     __syncthreads();
@@ -201,13 +197,13 @@ extern "C" int sedt_stitch_events(const int32_t* records, const int32_t* win_off
                                   int W, int W_stride, int R, int Q, int C, double merge_gap, int cap, int32_t* count, int32_t* out,
                                   int32_t* status, void* stream) {
   using namespace sedt;
-  SEDT_REQUIRE(Q >= 1 && Q <= SEDT_ST_MAXQ && C >= 1 && C <= SEDT_ST_MAXC, "stitch_events: Q=%d (1 .. %d) C=%d (1 .. %d)", Q, SEDT_ST_MAXQ,
-               C, SEDT_ST_MAXC);
-  SEDT_REQUIRE(K >= 1 && K <= SEDT_ST_MAXK, "stitch_events: %d thresholds (1 .. %d)", K, SEDT_ST_MAXK);
+  SEDT_REQUIRE(Q >= 1 && Q <= SEDT_MAX_QUERIES && C >= 1 && C <= SEDT_MAX_CLASSES, "stitch_events: Q=%d (1 .. %d) C=%d (1 .. %d)", Q, SEDT_MAX_QUERIES,
+               C, SEDT_MAX_CLASSES);
+  SEDT_REQUIRE(K >= 1 && K <= SEDT_MAX_THRESHOLDS, "stitch_events: %d thresholds (1 .. %d)", K, SEDT_MAX_THRESHOLDS);
   SEDT_REQUIRE(R >= 0 && W >= 0 && W <= W_stride, "stitch_events: R=%d W=%d W_stride=%d (0 <= W <= W_stride)", R, W, W_stride);
   SEDT_REQUIRE(merge_gap >= 0.0 && merge_gap < INFINITY, "stitch_events: merge_gap %.17g is not a finite number >= 0", merge_gap);
   SEDT_REQUIRE(cap >= 1, "stitch_events: cap=%d (>= 1)", cap);
-  SEDT_REQUIRE((double)K * R * C * cap * SEDT_ST_WORDS * 4.0 <= 4294967296.0, "stitch_events: an output of K=%d x R=%d x C=%d x cap=%d events "
+  SEDT_REQUIRE((double)K * R * C * cap * SEDT_EVENT_WORDS * 4.0 <= 4294967296.0, "stitch_events: an output of K=%d x R=%d x C=%d x cap=%d events "
                "is larger than 4 GiB", K, R, C, cap);
   SEDT_REQUIRE(records && win_off && win_start && rec_dur && count && out && status, "stitch_events: null pointer");
   SEDT_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "stitch_events: out is not 8-byte aligned");

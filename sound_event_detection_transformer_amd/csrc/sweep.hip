@@ -14,9 +14,6 @@
 
 namespace sedt {
 
-#define SEDT_SW_MAXK 1024          // thresholds per launch (gridDim.y)
-#define SEDT_SW_SLOT 5             // words of one event record {class, onset, offset, score, query}
-
 // block = 64 threads = one wave, blockIdx.x = clip of the batch, blockIdx.y = threshold of the grid; ev / tag: this fusion strategy's
 // [K][C][3]
 __global__ __launch_bounds__(64) void event_sweep_kernel(const int32_t* __restrict__ records, const int32_t* __restrict__ clip_idx,
@@ -25,14 +22,14 @@ __global__ __launch_bounds__(64) void event_sweep_kernel(const int32_t* __restri
                                                          const double* __restrict__ ref_end, int n_clips, int B, int Q, int C,
                                                          double t_collar, double pct, int optimal, unsigned long long* __restrict__ ev,
                                                          unsigned long long* __restrict__ tag) {
-  __shared__ int d_cls[SEDT_MT_MAXQ];                               // -1: not a live slot of a class 0 .. C - 1
-  __shared__ int r_cls[SEDT_MT_MAXR];
-  __shared__ double r_on[SEDT_MT_MAXR], r_end[SEDT_MT_MAXR];
-  __shared__ unsigned long long adj[SEDT_MT_MAXR];                  // adj[j] bit q: slot q hits reference j
-  __shared__ int match_est[SEDT_MT_MAXQ], from_ref[SEDT_MT_MAXQ], match_ref[SEDT_MT_MAXR];
-  __shared__ unsigned char queue[SEDT_MT_MAXC][SEDT_MT_MAXR];       // BFS queue of class c (refs of one class, one clip)
+  __shared__ int d_cls[SEDT_MAX_QUERIES];                               // -1: not a live slot of a class 0 .. C - 1
+  __shared__ int r_cls[SEDT_MAX_REF_EVENTS];
+  __shared__ double r_on[SEDT_MAX_REF_EVENTS], r_end[SEDT_MAX_REF_EVENTS];
+  __shared__ unsigned long long adj[SEDT_MAX_REF_EVENTS];                  // adj[j] bit q: slot q hits reference j
+  __shared__ int match_est[SEDT_MAX_QUERIES], from_ref[SEDT_MAX_QUERIES], match_ref[SEDT_MAX_REF_EVENTS];
+  __shared__ unsigned char queue[SEDT_MAX_CLASSES][SEDT_MAX_REF_EVENTS];       // BFS queue of class c (refs of one class, one clip)
   const int b = blockIdx.x, kt = blockIdx.y, lane = threadIdx.x;
-  const int32_t* rec = records + ((long)kt * B + b) * (1 + SEDT_SW_SLOT * Q);
+  const int32_t* rec = record_at(records, kt, B, b, Q);
   const int n = rec[0];
   if (n < 0 || n > Q) return;                                        // not a count decode_events writes: block-uniform
   int clip = clip_idx[b];
@@ -40,17 +37,17 @@ __global__ __launch_bounds__(64) void event_sweep_kernel(const int32_t* __restri
   int e0 = 0, ne = 0;
   if (clip >= 0) {
     e0 = ref_off[clip];
-    ne = min(max(ref_off[clip + 1] - e0, 0), SEDT_MT_MAXR);          // sedt_event_sweep_update bounds max_ref on the host
+    ne = min(max(ref_off[clip + 1] - e0, 0), SEDT_MAX_REF_EVENTS);          // sedt_event_sweep_update bounds max_ref on the host
   }
 
   // ---- stage: lane = slot of the record, lane = reference event
   int cls = -1;
   double on = 0.0, end = 0.0;
   if (lane < n) {
-    const int32_t* s = rec + 1 + SEDT_SW_SLOT * lane;
-    cls = s[0];
-    on = (double)__int_as_float(s[1]);
-    end = (double)__int_as_float(s[2]);
+    const int32_t* s = record_slot(rec, lane);
+    cls = s[SEDT_REC_CLASS];
+    on = (double)__int_as_float(s[SEDT_REC_ONSET]);
+    end = (double)__int_as_float(s[SEDT_REC_OFFSET]);
     if (cls < 0 || cls >= C) cls = -1;                               // never an index, not counted
   }
   d_cls[lane] = cls;
@@ -72,18 +69,9 @@ __global__ __launch_bounds__(64) void event_sweep_kernel(const int32_t* __restri
   for (int d = 0; d < n; ++d) n_sys += d_cls[d] == c;
   const long tp = event_class_match(c, ne, r_cls, adj, match_est, from_ref, match_ref, queue[c], optimal, nullptr, 0, n_ref);
   const long cell = ((long)kt * C + c) * 3;
-  if (clip >= 0) {
-    unsigned long long* e = ev + cell;
-    if (tp) atomicAdd(e, (unsigned long long)tp);
-    if (n_ref) atomicAdd(e + 1, (unsigned long long)n_ref);
-    if (n_sys) atomicAdd(e + 2, (unsigned long long)n_sys);
-  }
+  if (clip >= 0) add_counts3(ev + cell, tp, n_ref, n_sys);
   // ---- clip level: class present among the record's events / among the reference events; every clip counts
-  const bool ref_has = n_ref > 0, sys_has = n_sys > 0;
-  unsigned long long* t = tag + cell;
-  if (ref_has && sys_has) atomicAdd(t, 1ull);
-  if (!ref_has && sys_has) atomicAdd(t + 1, 1ull);
-  if (ref_has && !sys_has) atomicAdd(t + 2, 1ull);
+  add_presence(tag + cell, n_ref > 0, n_sys > 0);
 }
 
 }  // namespace sedt
@@ -93,13 +81,7 @@ extern "C" int sedt_event_sweep_update(const int32_t* records, const int32_t* cl
                                        int n_clips, int max_ref, int B, int Q, int C, int K, int n_fusion, int fusion, double t_collar,
                                        double pct, int optimal, int64_t* ev_counts, int64_t* tag_counts, void* stream) {
   using namespace sedt;
-  SEDT_REQUIRE(B >= 0 && Q >= 1 && Q <= SEDT_MT_MAXQ && C >= 1 && C <= SEDT_MT_MAXC, "event_sweep_update: B=%d Q=%d (<=%d) C=%d (<=%d)", B,
-               Q, SEDT_MT_MAXQ, C, SEDT_MT_MAXC);
-  SEDT_REQUIRE(K >= 1 && K <= SEDT_SW_MAXK, "event_sweep_update: %d thresholds (1 .. %d)", K, SEDT_SW_MAXK);
-  SEDT_REQUIRE(n_clips >= 0 && (n_clips == 0 || (ref_cls && ref_on && ref_end)), "event_sweep_update: reference table missing");
-  SEDT_REQUIRE(max_ref >= 0 && max_ref <= SEDT_MT_MAXR, "event_sweep_update: a clip has %d reference events (<= %d)", max_ref,
-               SEDT_MT_MAXR);
-  SEDT_REQUIRE(n_fusion >= 1 && fusion >= 0 && fusion < n_fusion, "event_sweep_update: fusion %d of %d", fusion, n_fusion);
+  if (clip_args_ok("event_sweep_update", B, Q, C, K, n_clips, ref_cls && ref_on && ref_end, max_ref, n_fusion, fusion)) return 1;
   if (B == 0) return 0;
   SEDT_REQUIRE(records && clip_idx && ref_off && ev_counts && tag_counts, "event_sweep_update: null pointer");
   const long mine = (long)fusion * K * C * 3;

@@ -761,14 +761,11 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
     ``decoder``) the PSDS confusion counts of the batch's records (clips ``clip_idx`` of its reference) are added on the device by the
     launch after the decode's.  With ``sweep`` (utilities.operating_points.SweepEventMetrics, bound to this ``decoder``) the event-based
     and clip-level counts of the batch's records at every threshold of the grid are added on the device in the same way."""
-    if psds is not None:
-        _check_psds(psds, decoder)
-        if clip_idx is None:
-            raise ValueError('predict_step(psds=...) needs the clip indices of the batch (clip_idx)')
-    if sweep is not None:
-        _check_sweep(sweep, decoder)
-        if clip_idx is None:
-            raise ValueError('predict_step(sweep=...) needs the clip indices of the batch (clip_idx)')
+    for name, scorer in (('psds', psds), ('sweep', sweep)):
+        if scorer is not None:
+            _check_bound(name, scorer, decoder)
+            if clip_idx is None:
+                raise ValueError(f'predict_step({name}=...) needs the clip indices of the batch (clip_idx)')
     with torch.no_grad():
         outputs = model(batch_input)
         B = outputs['pred_logits'].shape[0]
@@ -782,16 +779,24 @@ def predict_step(model, criterion, postprocessor, batch_input, targets, fusion_s
             _check_metrics(metrics, fusion_strategy)
             if clip_idx is None:
                 raise ValueError('predict_step(metrics=...) needs the clip indices of the batch (clip_idx)')
-            metrics.update(results, audio_tags, clip_idx)
-        if decoder is not None:
-            _check_decoder(decoder, fusion_strategy)
-            decoded = decoder.decode(results, audio_tags)
-            if psds is not None:
-                psds.update(decoded, clip_idx)
-            if sweep is not None:
-                sweep.update(decoded, clip_idx)
+        if _score(results, audio_tags, clip_idx, metrics, decoder, psds, sweep) is not None:
             return loss_dict, audio_tags, results, decoder.fetch()
     return loss_dict, audio_tags, results
+
+
+def _score(results, audio_tags, clip_idx, metrics, decoder, psds, sweep):
+    """what follows PostProcess in a predict step, eager or captured, in this order: metrics, decode, psds, sweep -> decoded or None"""
+    if metrics is not None:
+        metrics.update(results, audio_tags, clip_idx)
+    if decoder is None:
+        return None
+    _check_decoder(decoder, tuple(results))                 # the keys of ``results``: the fusion strategies the step ran, in its order
+    decoded = decoder.decode(results, audio_tags)
+    if psds is not None:
+        psds.update(decoded, clip_idx)
+    if sweep is not None:
+        sweep.update(decoded, clip_idx)
+    return decoded
 
 
 def _check_metrics(metrics, fusion_strategy):
@@ -804,14 +809,9 @@ def _check_decoder(decoder, fusion_strategy):
         raise ValueError(f'EventDecoder decodes fusion strategies {decoder.fusion}, the predict step runs {tuple(fusion_strategy)}')
 
 
-def _check_psds(psds, decoder):
-    if decoder is None or psds.decoder is not decoder:
-        raise ValueError('psds= scores the event records of the EventDecoder it was built with: pass that decoder as decoder=')
-
-
-def _check_sweep(sweep, decoder):
-    if decoder is None or sweep.decoder is not decoder:
-        raise ValueError('sweep= scores the event records of the EventDecoder it was built with: pass that decoder as decoder=')
+def _check_bound(name, scorer, decoder):
+    if decoder is None or scorer.decoder is not decoder:
+        raise ValueError(f'{name}= scores the event records of the EventDecoder it was built with: pass that decoder as decoder=')
 
 
 class GraphedPredictStep(object):
@@ -851,15 +851,16 @@ class GraphedPredictStep(object):
         if decoder is not None:
             _check_decoder(decoder, self.fusion)
         if psds is not None:
-            _check_psds(psds, decoder)
+            _check_bound('psds', psds, decoder)
         if sweep is not None:
-            _check_sweep(sweep, decoder)
+            _check_bound('sweep', sweep, decoder)
         self.counted = [m for m in (metrics, psds, sweep) if m is not None]   # what counts per clip: each takes the batch's clip indices
         for m in self.counted:
             if m is metrics:
                 _check_metrics(metrics, self.fusion)
             if m.table is None:
                 raise RuntimeError('GraphedPredictStep(metrics= / psds= / sweep=...): call set_reference() on it before building the step')
+        self.clip_idx = None
         if self.counted:
             self.clip_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.counted_gen = [m.generation for m in self.counted]
@@ -882,14 +883,8 @@ class GraphedPredictStep(object):
             losses = self.criterion.compute(outputs, dense)
             tags = (outputs['at'] > 0.5).long() if self.at else None
             res = {m: self.post.batched(outputs, self.sizes, audio_tags=tags, at_m=m, threshold=self.threshold) for m in self.fusion}
-            if self.metrics is not None:
-                self.metrics.update(res, tags, self.clip_idx)
-            if self.decoder is not None:
-                self.decoded = self.decoder.decode(res, tags)           # the static buffers the captured launches fill
-                if self.psds is not None:
-                    self.psds.update(self.decoded, self.clip_idx)
-                if self.sweep is not None:
-                    self.sweep.update(self.decoded, self.clip_idx)
+            # decoded: the static buffers the captured launches fill
+            self.decoded = _score(res, tags, self.clip_idx, self.metrics, self.decoder, self.psds, self.sweep)
         return losses, tags, res
 
     def __call__(self, batch_input, targets, clip_idx=None):
@@ -902,7 +897,8 @@ class GraphedPredictStep(object):
             if [m.generation for m in self.counted] != self.counted_gen:
                 raise RuntimeError('GraphedPredictStep: the metrics\' reference changed shape after the step was built; build a new step')
             if not (torch.is_tensor(clip_idx) and clip_idx.is_cuda):
-                clip_idx = [m.host_clip_index(clip_idx) for m in self.counted][0]       # checked against every table
+                first = {id(m.reference): m for m in reversed(self.counted)}     # once per distinct table, by its first holder
+                clip_idx = [m.host_clip_index(clip_idx) for m in reversed(first.values())][0]
             self.clip_idx.copy_(clip_idx, non_blocking=True)
         self.graph.replay()
         if self.decoder is not None:
@@ -1096,10 +1092,10 @@ def get_sedt_predictions(model, criterion, postprocessor, batches, decoder, file
         _check_metrics(metrics, fusion)
         metrics.reset()
     if psds is not None:
-        _check_psds(psds, decoder)
+        _check_bound('psds', psds, decoder)
         psds.reset()
     if sweep is not None:
-        _check_sweep(sweep, decoder)
+        _check_bound('sweep', sweep, decoder)
         sweep.reset()
     counted = metrics is not None or psds is not None or sweep is not None
     tag_table, sets = P.TagTable(), decoder.prediction_sets()

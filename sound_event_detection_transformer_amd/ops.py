@@ -1842,6 +1842,15 @@ def pseudo_labels(logits, boxes, at, thr, min_len, tables, counter=None, del_ove
                                         _p(counter), cap, L.stream_ptr()), 'pseudo_labels')
 
 
+def _clip_table_args(clip_idx, B, table, n_clips, dur=False):
+    """the asserts the three clip-level scoring launches share: clip indices and utilities.scoring.ClipReference's device table"""
+    assert clip_idx.dtype == torch.int32 and clip_idx.numel() == B and clip_idx.is_contiguous()
+    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_clips + 1
+    assert table['present'].dtype == torch.int32 and table['present'].numel() >= n_clips
+    assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
+    assert not dur or (table['dur'].dtype == torch.float64 and table['dur'].numel() >= n_clips)
+
+
 def event_metrics_update(scores, labels, boxes, at_tags, clip_idx, table, n_clips, max_ref, ev_counts, tag_counts, fusion,
                          threshold=0.5, min_duration=0.2, max_len=10.0, t_collar=0.2, pct=0.2, del_overlap=True, optimal=True,
                          seg_counts=None, sdi_counts=None, time_resolution=1.0, n_seg_words=1):
@@ -1856,12 +1865,10 @@ def event_metrics_update(scores, labels, boxes, at_tags, clip_idx, table, n_clip
     nf, C = ev_counts.shape[0], ev_counts.shape[1]
     assert scores.dtype == torch.float32 and labels.dtype == torch.int64 and boxes.dtype == torch.float32
     assert scores.is_contiguous() and labels.is_contiguous() and boxes.is_contiguous() and tuple(boxes.shape) == (B, Q, 2)
-    assert tuple(labels.shape) == (B, Q) and clip_idx.dtype == torch.int32 and clip_idx.numel() == B and clip_idx.is_contiguous()
+    assert tuple(labels.shape) == (B, Q)
+    _clip_table_args(clip_idx, B, table, n_clips)
     assert ev_counts.dtype == torch.int64 and tuple(ev_counts.shape) == (nf, C, 3) and ev_counts.is_contiguous()
     assert tag_counts.dtype == torch.int64 and tuple(tag_counts.shape) == (nf + 1, C, 3) and tag_counts.is_contiguous()
-    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_clips + 1
-    assert table['present'].dtype == torch.int32 and table['present'].numel() >= n_clips
-    assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
     if at_tags is not None:
         assert at_tags.dtype == torch.int64 and tuple(at_tags.shape) == (B, C) and at_tags.is_contiguous() and at_tags.is_cuda
     if seg_counts is None:
@@ -1882,7 +1889,7 @@ def event_metrics_update(scores, labels, boxes, at_tags, clip_idx, table, n_clip
         float(time_resolution), int(n_seg_words), _p(seg_counts), _p(sdi_counts), L.stream_ptr()), 'event_segment_metrics_update')
 
 
-DECODE_MAX_THRESHOLDS = 1024      # csrc/decode.hip: SEDT_DE_MAXK
+DECODE_MAX_THRESHOLDS = 1024      # csrc/event_records.h: SEDT_MAX_THRESHOLDS
 
 
 def decode_events_views(packed, Q):
@@ -1928,13 +1935,10 @@ def event_sweep_update(records, clip_idx, table, n_clips, max_ref, n_classes, ev
     C = int(n_classes)
     Q = (records.shape[2] - 1) // 5
     assert records.dtype == torch.int32 and records.dim() == 3 and records.shape[2] == 1 + 5 * Q and records.is_contiguous()
-    assert clip_idx.dtype == torch.int32 and clip_idx.numel() == B and clip_idx.is_contiguous()
+    _clip_table_args(clip_idx, B, table, n_clips)
     nf = ev_counts.shape[0]
     assert ev_counts.dtype == torch.int64 and tuple(ev_counts.shape) == (nf, K, C, 3) and ev_counts.is_contiguous()
     assert tag_counts.dtype == torch.int64 and tuple(tag_counts.shape) == (nf, K, C, 3) and tag_counts.is_contiguous()
-    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_clips + 1
-    assert table['present'].dtype == torch.int32 and table['present'].numel() >= n_clips
-    assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
     L.check(L.load().sedt_event_sweep_update(_p(records), _p(clip_idx), _p(table['present']), _p(table['off']), _p(table['cls']),
                                              _p(table['on']), _p(table['end']), int(n_clips), int(max_ref), B, Q, C, K, nf, int(fusion),
                                              float(t_collar), float(pct), int(bool(optimal)), _p(ev_counts), _p(tag_counts),
@@ -1951,13 +1955,9 @@ def psds_update(records, clip_idx, table, n_clips, max_ref, n_classes, counts, f
     C = int(n_classes)
     Q = (records.shape[2] - 1) // 5
     assert records.dtype == torch.int32 and records.dim() == 3 and records.shape[2] == 1 + 5 * Q and records.is_contiguous()
-    assert clip_idx.dtype == torch.int32 and clip_idx.numel() == B and clip_idx.is_contiguous()
+    _clip_table_args(clip_idx, B, table, n_clips, dur=True)
     nf = counts.shape[0]
     assert counts.dtype == torch.int64 and tuple(counts.shape) == (nf, K, C, C + 1) and counts.is_contiguous()
-    assert table['off'].dtype == torch.int32 and table['off'].numel() >= n_clips + 1
-    assert table['present'].dtype == torch.int32 and table['present'].numel() >= n_clips
-    assert table['cls'].dtype == torch.int32 and table['on'].dtype == torch.float64 and table['end'].dtype == torch.float64
-    assert table['dur'].dtype == torch.float64 and table['dur'].numel() >= n_clips
     L.check(L.load().sedt_psds_update(_p(records), _p(clip_idx), _p(table['present']), _p(table['off']), _p(table['cls']), _p(table['on']),
                                       _p(table['end']), _p(table['dur']), int(n_clips), int(max_ref), B, Q, C, K, nf, int(fusion),
                                       float(dtc), float(gtc), float(cttc), _p(counts), L.stream_ptr()), 'psds_update')

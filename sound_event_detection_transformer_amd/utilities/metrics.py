@@ -39,8 +39,8 @@ import numpy as np
 import torch
 
 from .. import ops
+from .scoring import GENERATION, MAX_REF_EVENTS, ClipReference, ClipScorer, read_back    # noqa: F401 (MAX_REF_EVENTS: importers)
 
-MAX_REF_EVENTS = 64        # reference events of one clip the kernel holds (csrc/metrics.hip: SEDT_EM_MAXR)
 MAX_SEGMENTS = 1024        # segments of one clip the segment-based counts hold (csrc/metrics.hip: SEDT_EM_MAXSEG)
 SUMMARY_COLUMNS = ('Eb_F1', 'Eb_P', 'Eb_R', 'Sb_F', 'Sb_P', 'Sb_R', 'At_F1')      # the reference's "All Metrics" row
 
@@ -62,7 +62,7 @@ def _ratio(a, b):
     return float(a) / float(b) if b else 0.0
 
 
-class EventMetrics(object):
+class EventMetrics(ClipScorer):
     """engine.evaluate's scores accumulated on the device.  ``labels``: the class names in the model's class order (decoder.labels);
     ``fusion_strategy``: the PostProcess fusion modes the predict step runs, in its order (results are keyed by them);
     ``time_resolution``: seconds per segment of the segment-based scores, None for none."""
@@ -70,7 +70,6 @@ class EventMetrics(object):
     def __init__(self, labels, max_len_seconds, t_collar=0.2, percentage_of_length=0.2, threshold=0.5, min_duration=0.2,
                  del_overlap=True, fusion_strategy=(1,), optimal=True, device=None, time_resolution=None):
         self.labels = list(labels)
-        self.index = {l: i for i, l in enumerate(self.labels)}
         self.C = len(self.labels)
         assert 1 <= self.C <= 63, 'EventMetrics: 1..63 classes'
         self.max_len = float(max_len_seconds)
@@ -87,79 +86,45 @@ class EventMetrics(object):
         if self.time_resolution is not None:
             self.seg = torch.zeros((nf, self.C, 3), dtype=torch.int64, device=self.device)
             self.sdi = torch.zeros((nf, 3), dtype=torch.int64, device=self.device)
-        self.table, self.n_clips, self.max_ref, self.n_seg_words = None, 0, 0, 0
-        self.generation = 0          # bumped when set_reference changes what a launch captured: table pointers, clip / event / segment counts
-        self.at_counted = False
+        self.n_seg_words, self.at_counted = 0, False
+        self._bind(ClipReference(self.labels, self.device))
 
     # ------------------------------------------------------------------------------------------------------------------------
-    def set_reference(self, events):
-        """events: per clip (the index ``update`` receives) a list of (label, onset, offset) - label a class name or index, times in
-        seconds - or None for a clip that has no row in the reference.  Uploads the table once; the counters are not touched."""
-        seg = self.time_resolution is not None
-        if seg and not (math.isfinite(self.time_resolution) and self.time_resolution > 0):
+    def _segment_words(self, host, n_events):
+        """this scorer's own checks on a reference's host arrays: the 64-segment words of a clip, 0 without time_resolution"""
+        if self.time_resolution is None:
+            return 0
+        if not (math.isfinite(self.time_resolution) and self.time_resolution > 0):
             raise ValueError(f'set_reference: time_resolution {self.time_resolution!r} is not a positive number of seconds')
-        off, cls, on, end, present = [0], [], [], [], []
-        for k, ev in enumerate(events):
-            present.append(ev is not None)
-            for label, onset, offset in (ev or ()):
-                c = self.index[label] if label in self.index else int(label)
-                if not 0 <= c < self.C:
-                    raise ValueError(f'set_reference: clip {k}: class {label!r} is not one of the {self.C} labels')
-                if not (math.isfinite(onset) and math.isfinite(offset)):
-                    raise ValueError(f'set_reference: clip {k}: non-finite event time')
-                if seg and (onset < 0 or offset < 0):
-                    raise ValueError(f'set_reference: clip {k}: negative event time ({onset}, {offset}) in a segment-based evaluation')
-                cls.append(c), on.append(float(onset)), end.append(float(offset))
-            if len(cls) - off[-1] > MAX_REF_EVENTS:
-                raise ValueError(f'set_reference: clip {k} has {len(cls) - off[-1]} reference events (at most {MAX_REF_EVENTS})')
-            off.append(len(cls))
-        words = 0
-        if seg:
-            q = max([self.max_len] + end) * 1 / self.time_resolution          # the longest event roll, as sed_eval sizes it
-            if not q <= MAX_SEGMENTS:
-                raise ValueError(f'set_reference: {max([self.max_len] + end)} s at time_resolution {self.time_resolution} s is more '
-                                 f'than {MAX_SEGMENTS} segments per clip')
-            words = max(1, -(-math.ceil(q) // 64))
-        n = len(off) - 1
-        max_ref = int(np.diff(off).max()) if n else 0
-        host = {'present': torch.tensor(present or [0], dtype=torch.int32), 'off': torch.tensor(off, dtype=torch.int32),
-                'cls': torch.tensor(cls or [0], dtype=torch.int32), 'on': torch.tensor(on or [0.0], dtype=torch.float64), 'end': torch.tensor(end or [0.0], dtype=torch.float64)}
-        t = self.table
-        if t is not None and all(t[k].numel() >= host[k].numel() for k in host):
-            for k in host:
-                t[k][:host[k].numel()].copy_(host[k])
-        else:
-            self.table = {k: v.to(self.device) for k, v in host.items()}
-            self.generation += 1
-        if (n, max_ref, words) != (self.n_clips, self.max_ref, self.n_seg_words):
-            self.generation += 1
-        self.n_clips, self.max_ref, self.n_seg_words = n, max_ref, words
-        return self
+        on, end = host['on'][:n_events], host['end'][:n_events]
+        bad = np.nonzero((on < 0) | (end < 0))[0]
+        if bad.size:
+            j = int(bad[0])
+            k = int(np.searchsorted(host['off'], j, side='right')) - 1
+            raise ValueError(f'set_reference: clip {k}: negative event time ({on[j]}, {end[j]}) in a segment-based evaluation')
+        longest = max([self.max_len] + end.tolist())
+        q = longest * 1 / self.time_resolution                              # the longest event roll, as sed_eval sizes it
+        if not q <= MAX_SEGMENTS:
+            raise ValueError(f'set_reference: {longest} s at time_resolution {self.time_resolution} s is more '
+                             f'than {MAX_SEGMENTS} segments per clip')
+        return max(1, -(-math.ceil(q) // 64))
 
-    def host_clip_index(self, idx):
-        """the batch's clip indices as a host int32 tensor, checked against the table (-1 = a clip outside it, not evaluated)"""
-        h = torch.as_tensor(np.asarray(idx, dtype=np.int64)).reshape(-1)
-        bad = (h < -1) | (h >= self.n_clips)
-        if bool(bad.any()):
-            raise ValueError(f'EventMetrics: clip index {int(h[bad][0])} outside -1 .. {self.n_clips - 1}')
-        return h.to(torch.int32)
+    _accepts = _segment_words         # asked before the reference changes, whoever sets it: a refusal leaves the table as it was
 
-    def clip_index(self, idx):
-        """the batch's clip indices as a device int32 tensor (a device tensor is taken as it is: the kernel skips indices outside
-        the table)"""
-        if torch.is_tensor(idx) and idx.is_cuda:
-            return idx.to(torch.int32).contiguous()
-        return self.host_clip_index(idx).to(self.device)
+    def _adopted(self):
+        """the table was set, or the scorer holds another: the segment words follow it, and with them the generation"""
+        ref = self.reference
+        words = 0 if ref.host is None else self._segment_words(ref.host, ref.n_events)
+        if words != self.n_seg_words:
+            self.n_seg_words, self._generation = words, next(GENERATION)
 
     def counters(self):
         """every device counter tensor: [ev, tag] (+ [seg, sdi] with segment-based scores)"""
         return [t for t in (self.ev, self.tag, self.seg, self.sdi) if t is not None]
 
-    def reset(self):
-        """zero the counters (start of a validation set); in place, so a captured graph keeps accumulating into them"""
-        for t in self.counters():
-            t.zero_()
-        return self
+    def _read(self):
+        """every counter as numpy int64, in the order of counters(): ONE device->host copy (scoring.read_back)"""
+        return read_back(self.counters())
 
     def update(self, results, audio_tags, clip_idx):
         """one batch: results {at_m: (scores [B,Q], labels [B,Q] int64, boxes [B,Q,2] seconds)} as predict_step returns them,
@@ -179,27 +144,15 @@ class EventMetrics(object):
                                      min_duration=self.min_duration, max_len=self.max_len, t_collar=self.t_collar, pct=self.pct,
                                      del_overlap=self.del_overlap, optimal=self.optimal, **seg)
 
-    def _read(self):
-        """every counter as numpy int64, in the order of counters(): ONE device->host copy"""
-        ts = self.counters()
-        h = torch.cat([t.reshape(-1) for t in ts]).cpu().numpy()
-        out, o = [], 0
-        for t in ts:
-            out.append(h[o:o + t.numel()].reshape(t.shape))
-            o += t.numel()
-        return out
-
     def counts(self):
         """(ev [n_fusion, C, 3] {tp, n_ref, n_sys}, tag [n_fusion + 1, C, 3] {tp, fp, fn}) as numpy int64: ONE device->host copy"""
-        ev, tag = self._read()[:2]
-        return ev, tag
+        return tuple(self._read()[:2])
 
     def segment_counts(self):
         """(seg [n_fusion, C, 3] {tp, n_ref, n_sys}, sdi [n_fusion, 3] {S, D, I}) as numpy int64, None without time_resolution"""
         if self.seg is None:
             return None
-        seg, sdi = self._read()[2:]
-        return seg, sdi
+        return tuple(self._read()[2:])
 
     def compute(self):
         """{at_m: {'f1', 'precision', 'recall', 'class_wise', 'clip': {...}[, 'segment': {...}]}, 'at': {...}}: event-based macro

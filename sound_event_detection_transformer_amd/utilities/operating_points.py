@@ -21,8 +21,9 @@ import numpy as np
 import torch
 
 from .. import ops
-from .metrics import MAX_REF_EVENTS, EventMetrics, _class_scores, _macro, _ratio, _tag_scores
+from .metrics import _class_scores, _macro, _ratio, _tag_scores
 from .predictions import operating_point
+from .scoring import ClipReference, ClipScorer, read_back
 
 
 def _grid_2d(threshold_values, K, C):
@@ -106,7 +107,7 @@ class SweepResult(object):
         return select_class_wise(self.ev, self.threshold_values, default)
 
 
-class SweepEventMetrics(object):
+class SweepEventMetrics(ClipScorer):
     """EventMetrics' event-based and clip-level counts at every operating point of ``decoder`` (a utilities.predictions.EventDecoder:
     its labels, its K thresholds, its fusion strategies), accumulated on the device from its event records.  ``t_collar``,
     ``percentage_of_length`` and ``optimal`` are EventMetrics'.  See the module docstring."""
@@ -118,66 +119,22 @@ class SweepEventMetrics(object):
         shape = (len(self.fusion), self.K, self.C, 3)
         self.ev = torch.zeros(shape, dtype=torch.int64, device=self.device)
         self.tag = torch.zeros(shape, dtype=torch.int64, device=self.device)
-        # the reference table is EventMetrics' (the same list, the same refusals, the same generation rule), uploaded by one of them
-        # that counts nothing itself
-        self._ref = EventMetrics(self.labels, decoder.max_len, fusion_strategy=self.fusion, device=self.device)
-
-    table = property(lambda self: self._ref.table)
-    n_clips = property(lambda self: self._ref.n_clips)
-    max_ref = property(lambda self: self._ref.max_ref)
-    generation = property(lambda self: self._ref.generation)    # bumped when set_reference changes what a launch captured
-
-    def set_reference(self, events):
-        """events: EventMetrics.set_reference's list - per clip (the index ``update`` receives) a list of (label, onset, offset), label
-        a class name or index, or None for a clip that has no row in the reference.  Uploads the table once; the counters are not
-        touched."""
-        self._ref.set_reference(events)
-        assert self._ref.max_ref <= MAX_REF_EVENTS
-        return self
-
-    def host_clip_index(self, idx):
-        """the batch's clip indices as a host int32 tensor, checked against the table (-1 = a clip outside it)"""
-        h = torch.as_tensor(np.asarray(idx, dtype=np.int64)).reshape(-1)
-        bad = (h < -1) | (h >= self.n_clips)
-        if bool(bad.any()):
-            raise ValueError(f'SweepEventMetrics: clip index {int(h[bad][0])} outside -1 .. {self.n_clips - 1}')
-        return h.to(torch.int32)
-
-    def clip_index(self, idx):
-        """the batch's clip indices as a device int32 tensor (a device tensor is taken as it is: the kernel treats indices outside
-        the table as clips without a reference row)"""
-        if torch.is_tensor(idx) and idx.is_cuda:
-            return idx.to(torch.int32).contiguous()
-        return self.host_clip_index(idx).to(self.device)
+        self.max_len = decoder.max_len
+        self._bind(ClipReference(self.labels, self.device))
 
     def counters(self):
         return [self.ev, self.tag]
 
-    def reset(self):
-        """zero the counters (start of a validation set, or of another threshold grid); in place, so a captured graph keeps
-        accumulating into them"""
-        self.ev.zero_()
-        self.tag.zero_()
-        return self
-
     def update(self, decoded, clip_idx):
-        """one batch: ``decoded`` is what ``EventDecoder.decode`` returned for it, clip_idx [B] the clips' indices in the reference
-        (-1 = no reference row).  One launch per fusion strategy on the records still on the device; nothing is read back."""
-        if self.table is None:
-            raise RuntimeError('SweepEventMetrics.update: set_reference() first')
-        ring = decoded[0]
-        idx = self.clip_index(clip_idx)
-        for i, m in enumerate(self.fusion):
-            records = ring['dev'][m]
-            if records.shape[0] != self.K:
-                raise ValueError(f'SweepEventMetrics.update: records of {records.shape[0]} thresholds, the counters hold {self.K}')
+        """one batch: what ``EventDecoder.decode`` returned for it and clip_idx [B], the clips' indices in the reference (-1: none).
+        One launch per fusion strategy on the records still on the device; nothing is read back."""
+        for i, records, idx in self._records(decoded, clip_idx):
             ops.event_sweep_update(records, idx, self.table, self.n_clips, self.max_ref, self.C, self.ev, self.tag, i,
                                    t_collar=self.t_collar, pct=self.pct, optimal=self.optimal)
 
     def counts(self):
         """(ev [n_fusion, K, C, 3] {tp, n_ref, n_sys}, tag [n_fusion, K, C, 3] {tp, fp, fn}) as numpy int64: ONE device->host copy"""
-        h = torch.stack([self.ev, self.tag]).cpu().numpy()
-        return h[0], h[1]
+        return tuple(read_back(self.counters()))
 
     def compute(self):
         """{at_m: SweepResult}: per fusion strategy the scores at every operating point of the decoder's grid as it stands; one

@@ -56,7 +56,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .metrics import MAX_REF_EVENTS
+from .scoring import ClipReference, ClipScorer, read_back
 
 SETTINGS = ((0, 0, 100), (1, 0, 100), (0, 1, 100))         # (alpha_ct, alpha_st, max_efpr) of the reference's psds_score
 
@@ -131,114 +131,50 @@ class PsdsResult(dict):
         return _curve(self['tpr'], self['fpr'], self['ctr'], self._valid, alpha_ct, alpha_st, max_efpr)[1:]
 
 
-class PsdsMetrics(object):
+def finish(counts, n_gt, gt_dur, total_dur, settings, thresholds):
+    """one fusion strategy's PsdsResult from its counts [K, C, C + 1] and the dataset constants: the PSD scores at ``settings``
+    ((alpha_ct, alpha_st, max_efpr) triples), the rates they come from and the decoder's ``thresholds``"""
+    tpr, fpr, ctr, valid = _rates(counts, n_gt, gt_dur, total_dur)
+    r = PsdsResult(psds={tuple(s): _curve(tpr, fpr, ctr, valid, *s)[0] for s in settings}, tpr=tpr, fpr=fpr, ctr=ctr,
+                   thresholds=thresholds)
+    r._valid = valid
+    return r
+
+
+class PsdsMetrics(ClipScorer):
     """PSDS accumulated on the device from ``decoder``'s event records (a utilities.predictions.EventDecoder: its labels, its K
     thresholds - one operating point each - and its fusion strategies).  See the module docstring for what is counted."""
 
     def __init__(self, decoder, dtc_threshold=0.5, gtc_threshold=0.5, cttc_threshold=0.3):
         self.decoder = decoder
         self.labels, self.C, self.K, self.fusion, self.device = decoder.labels, decoder.C, decoder.K, decoder.fusion, decoder.device
-        self.index = {l: i for i, l in enumerate(self.labels)}
         self.dtc, self.gtc, self.cttc = float(dtc_threshold), float(gtc_threshold), float(cttc_threshold)
         if any(math.isnan(t) for t in (self.dtc, self.gtc, self.cttc)):
             raise ValueError('PsdsMetrics: a tolerance criterion is NaN')
         self.counts = torch.zeros((len(self.fusion), self.K, self.C, self.C + 1), dtype=torch.int64, device=self.device)
-        self.table, self.n_clips, self.max_ref = None, 0, 0
-        self.n_gt, self.gt_dur, self.total_dur = None, None, 0.0
-        self.generation = 0          # bumped when set_reference changes what a launch captured: table pointers, clip / event counts
+        self.max_len = decoder.max_len
+        self._bind(ClipReference(self.labels, self.device))
 
-    # ------------------------------------------------------------------------------------------------------------------------
+    n_gt = property(lambda self: self.reference.n_gt)               # PSDS' n_c, T_c and T: the reference's
+    gt_dur = property(lambda self: self.reference.gt_dur)
+    total_dur = property(lambda self: self.reference.total_dur)
+
     def set_reference(self, events, durations=None):
-        """events: EventMetrics.set_reference's list - per clip (the index ``update`` receives) a list of (label, onset, offset), label
-        a class name or index, or None for a clip that has no row in the reference; durations: per clip its length in seconds (None:
-        the decoder's max_len_seconds for every clip).  Uploads the table once and takes n_c, T_c and T from it; the counters are
-        not touched."""
-        events = list(events)
-        if durations is None:
-            durations = [self.decoder.max_len] * len(events)
-        durations = [float(d) for d in durations]
-        if len(durations) != len(events):
-            raise ValueError(f'set_reference: {len(durations)} durations for {len(events)} clips')
-        off, cls, on, end, present = [0], [], [], [], []
-        n_gt, gt_dur, total = np.zeros(self.C, np.int64), np.zeros(self.C, np.float64), 0.0
-        for k, ev in enumerate(events):
-            present.append(ev is not None)
-            if not (math.isfinite(durations[k]) and durations[k] >= 0):
-                raise ValueError(f'set_reference: clip {k}: duration {durations[k]!r} is not a finite non-negative number of seconds')
-            if ev is not None:
-                total += durations[k]
-            for label, onset, offset in (ev or ()):
-                c = self.index[label] if label in self.index else int(label)
-                if not 0 <= c < self.C:
-                    raise ValueError(f'set_reference: clip {k}: class {label!r} is not one of the {self.C} labels')
-                if not (math.isfinite(onset) and math.isfinite(offset)):
-                    raise ValueError(f'set_reference: clip {k}: non-finite event time')
-                cls.append(c), on.append(float(onset)), end.append(float(offset))
-                if end[-1] - on[-1] > 0:                               # a zero-length event takes part in nothing
-                    n_gt[c] += 1
-                    gt_dur[c] += end[-1] - on[-1]
-            if len(cls) - off[-1] > MAX_REF_EVENTS:
-                raise ValueError(f'set_reference: clip {k} has {len(cls) - off[-1]} reference events (at most {MAX_REF_EVENTS})')
-            off.append(len(cls))
-        n = len(off) - 1
-        max_ref = int(np.diff(off).max()) if n else 0
-        host = {'present': torch.tensor(present or [0], dtype=torch.int32), 'off': torch.tensor(off, dtype=torch.int32),
-                'cls': torch.tensor(cls or [0], dtype=torch.int32), 'on': torch.tensor(on or [0.0], dtype=torch.float64),
-                'end': torch.tensor(end or [0.0], dtype=torch.float64), 'dur': torch.tensor(durations or [0.0], dtype=torch.float64)}
-        t = self.table
-        if t is not None and all(t[k].numel() >= host[k].numel() for k in host):
-            for k in host:
-                t[k][:host[k].numel()].copy_(host[k])
-        else:
-            self.table = {k: v.to(self.device) for k, v in host.items()}
-            self.generation += 1
-        if (n, max_ref) != (self.n_clips, self.max_ref):
-            self.generation += 1
-        self.n_clips, self.max_ref = n, max_ref
-        self.n_gt, self.gt_dur, self.total_dur = n_gt, gt_dur, total
-        return self
-
-    def host_clip_index(self, idx):
-        """the batch's clip indices as a host int32 tensor, checked against the table (-1 = a clip outside it, not scored)"""
-        h = torch.as_tensor(np.asarray(idx, dtype=np.int64)).reshape(-1)
-        bad = (h < -1) | (h >= self.n_clips)
-        if bool(bad.any()):
-            raise ValueError(f'PsdsMetrics: clip index {int(h[bad][0])} outside -1 .. {self.n_clips - 1}')
-        return h.to(torch.int32)
-
-    def clip_index(self, idx):
-        """the batch's clip indices as a device int32 tensor (a device tensor is taken as it is: the kernel skips indices outside
-        the table)"""
-        if torch.is_tensor(idx) and idx.is_cuda:
-            return idx.to(torch.int32).contiguous()
-        return self.host_clip_index(idx).to(self.device)
+        return self._set_reference(events, durations)
 
     def counters(self):
         return [self.counts]
 
-    def reset(self):
-        """zero the counters (start of a validation set, or of another threshold grid); in place, so a captured graph keeps
-        accumulating into them"""
-        self.counts.zero_()
-        return self
-
     def update(self, decoded, clip_idx):
-        """one batch: ``decoded`` is what ``EventDecoder.decode`` returned for it, clip_idx [B] the clips' indices in the reference
-        (-1 = no reference row).  One launch per fusion strategy on the records still on the device; nothing is read back."""
-        if self.table is None:
-            raise RuntimeError('PsdsMetrics.update: set_reference() first')
-        ring = decoded[0]
-        idx = self.clip_index(clip_idx)
-        for i, m in enumerate(self.fusion):
-            records = ring['dev'][m]
-            if records.shape[0] != self.K:
-                raise ValueError(f'PsdsMetrics.update: records of {records.shape[0]} thresholds, the counters hold {self.K}')
+        """one batch: what ``EventDecoder.decode`` returned for it and clip_idx [B], the clips' indices in the reference (-1: none).
+        One launch per fusion strategy on the records still on the device; nothing is read back."""
+        for i, records, idx in self._records(decoded, clip_idx):
             ops.psds_update(records, idx, self.table, self.n_clips, self.max_ref, self.C, self.counts, i, dtc=self.dtc, gtc=self.gtc,
                             cttc=self.cttc)
 
     def counts_host(self):
         """counts [n_fusion, K, C, C + 1] as numpy int64: ONE device->host copy"""
-        return self.counts.cpu().numpy()
+        return read_back(self.counters())[0]
 
     def compute(self, settings=SETTINGS):
         """{at_m: PsdsResult}: per fusion strategy the PSD scores at ``settings`` ((alpha_ct, alpha_st, max_efpr) triples; the default
@@ -246,11 +182,5 @@ class PsdsMetrics(object):
         if self.n_gt is None:
             raise RuntimeError('PsdsMetrics.compute: set_reference() first')
         counts = self.counts_host()
-        res = {}
-        for i, m in enumerate(self.fusion):
-            tpr, fpr, ctr, valid = _rates(counts[i], self.n_gt, self.gt_dur, self.total_dur)
-            r = PsdsResult(psds={tuple(s): _curve(tpr, fpr, ctr, valid, *s)[0] for s in settings}, tpr=tpr, fpr=fpr, ctr=ctr,
-                           thresholds=self.decoder.operating_points())
-            r._valid = valid
-            res[m] = r
-        return res
+        return {m: finish(counts[i], self.n_gt, self.gt_dur, self.total_dur, settings, self.decoder.operating_points())
+                for i, m in enumerate(self.fusion)}

@@ -14,7 +14,7 @@ import torch
 
 from .. import ops
 from .predictions import COLUMNS, operating_point
-from .transforms import PinnedRing
+from .scoring import Uploads
 
 MAX_OUTPUT_BYTES = 1 << 30        # the stitched event buffer of one fusion strategy
 DEFAULT_CAP = 4096
@@ -240,7 +240,7 @@ class RecordingDetector(object):
         self.amp = torch.zeros((self.B, 1 + self.window // mel.hop, mel.F), dtype=torch.float32, device=self.dev)
         self.sizes = torch.full((self.B,), self.window_seconds, dtype=torch.float32, device=self.dev)
         self.step = None
-        self._up, self._host, self._serial, self._keep = {}, None, 0, None
+        self._up, self._host, self._serial, self._keep = Uploads(self.dev), None, 0, None
         self.resample_quality, self._resamplers = resample_quality, {}
 
     # ------------------------------------------------------------------ pieces
@@ -299,15 +299,6 @@ class RecordingDetector(object):
             return self.step(None)                      # the warm-up ran on this batch; the replay fills the outputs from it
         return self.step(None if x is self.step.static_x else x)
 
-    def _upload(self, name, host):
-        """a small table to the device through a ring of pinned staging buffers of its own (transforms.PinnedRing)"""
-        ring = self._up.get(name)
-        if ring is None:
-            ring = self._up[name] = PinnedRing(self.dev)
-        host = np.ascontiguousarray(host)
-        raw = ring.upload(host.view(np.uint8).reshape(-1))
-        return raw[:host.nbytes].view({np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64}[host.dtype])
-
     # ------------------------------------------------------------------ the call
     def records(self, waves, sample_rates=None):
         """windows -> the per-window event records: ({at_m: int32 [K, W, 1 + 5 Q] on the device}, tags (W, C) int64 on the device or
@@ -350,9 +341,9 @@ class RecordingDetector(object):
         Q = (next(iter(rec.values())).shape[2] - 1) // 5
         cap = int(self.cap) if self.cap is not None else min(DEFAULT_CAP, max(int(np.diff(win_off).max(initial=1)), 1) * Q)
         check_output_bytes(self.decoder.K, R, self.decoder.C, cap)
-        d_off = self._upload('off', win_off)
-        d_t = self._upload('t', t)
-        d_dur = self._upload('dur', dur)
+        d_off = self._up('off', win_off)
+        d_t = self._up('t', t)
+        d_dur = self._up('dur', dur)
         res = {m: ops.stitch_events(rec[m], d_off, d_t, d_dur, self.decoder.C, self.merge_gap, cap, n_windows=W) for m in rec}
         return res, cap
 

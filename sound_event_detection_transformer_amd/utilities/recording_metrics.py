@@ -39,49 +39,9 @@ from .. import ops
 from .metrics import finalize
 from .operating_points import select_class_wise
 from .predictions import operating_point
-from .transforms import PinnedRing
+from .scoring import STATUS_REASONS, RecordingReference, RecordingScorer, Uploads, reference_table, status_error    # noqa: F401
 
 MAX_WORDS = (1 << 25) - 1          # 64-segment words of one recording (csrc/recmetrics.hip: SEDT_RM_MAXWORDS)
-STATUS_REASONS = {1: 'its stitched lists are not complete (a stitch status was raised, or a class holds more events than cap)',
-                  2: 'more than 64 reference events or 64 estimates of one class lie in one block of onsets chained within t_collar',
-                  4: 'an event list is not ascending by onset or holds a non-finite time'}
-
-
-def reference_table(reference, labels, segments=False):
-    """{filename: [(label, onset, offset), ...]} -> the CSR table over (reference recording, class) the kernels read, as host arrays:
-    {'names' (the filenames in the dict's order), 'index' {filename: i}, 'off' int32 [N * C + 1], 'on' / 'end' float64 [E] (per
-    (recording, class) sorted by (onset, offset, input order)), 'max_end' float64 [N] (0 for an empty list)}.  label: a class name or
-    index.  Unknown labels and non-finite times are refused, with ``segments`` negative times too."""
-    labels = list(labels)
-    index, C = {l: i for i, l in enumerate(labels)}, len(labels)
-    names, off, on, end, max_end = [], [0], [], [], []
-    for name, events in reference.items():
-        per = [[] for _ in range(C)]
-        for n, (label, onset, offset) in enumerate(events):
-            if label in index:
-                c = index[label]
-            elif isinstance(label, (int, np.integer)) and 0 <= int(label) < C:
-                c = int(label)
-            else:
-                raise ValueError(f'set_reference: recording {name!r}: class {label!r} is not one of the {C} labels')
-            onset, offset = float(onset), float(offset)
-            if not (math.isfinite(onset) and math.isfinite(offset)):
-                raise ValueError(f'set_reference: recording {name!r}: non-finite event time ({onset}, {offset})')
-            if segments and (onset < 0 or offset < 0):
-                raise ValueError(f'set_reference: recording {name!r}: negative event time ({onset}, {offset}) in a segment-based '
-                                 'evaluation')
-            per[c].append((onset, offset, n))
-        for c in range(C):
-            per[c].sort()
-            on += [e[0] for e in per[c]]
-            end += [e[1] for e in per[c]]
-            off.append(len(on))
-        names.append(name)
-        max_end.append(max([e[1] for p in per for e in p], default=0.0))
-    if len(on) > 2 ** 31 - 1:
-        raise ValueError(f'set_reference: {len(on)} reference events exceed int32 indexing')
-    return {'names': names, 'index': {n: i for i, n in enumerate(names)}, 'off': np.asarray(off, np.int32),
-            'on': np.asarray(on, np.float64), 'end': np.asarray(end, np.float64), 'max_end': np.asarray(max_end, np.float64)}
 
 
 def segment_words(rec_dur, max_end, time_resolution):
@@ -94,16 +54,6 @@ def segment_words(rec_dur, max_end, time_resolution):
     return words
 
 
-def status_error(status, filenames, thresholds, what):
-    """None, or the RuntimeError for the first non-zero entry of a launch's status [K, R]"""
-    bad = np.argwhere(np.asarray(status) != 0)
-    if not len(bad):
-        return None
-    k, r = (int(v) for v in bad[0])
-    s = int(status[k][r])
-    return RuntimeError(f'{what}: recording {filenames[r]!r} at threshold {thresholds[k]}: status {s} ({STATUS_REASONS.get(s, "unknown")})')
-
-
 def finish(ev, tag, labels, fusion, seg=None, sdi=None):
     """counter arrays ev / tag [n_fusion, K, C, 3] (and seg [n_fusion, K, C, 3], sdi [n_fusion, K, 3]) -> {at_m: [per threshold what
     utilities.metrics.finalize returns for that threshold's slices]}: the recording-level presence scores under its 'clip' key"""
@@ -113,7 +63,7 @@ def finish(ev, tag, labels, fusion, seg=None, sdi=None):
     return {m: [per_k[k][m] for k in range(K)] for m in fusion}
 
 
-class RecordingMetrics(object):
+class RecordingMetrics(RecordingScorer):
     """event-based, recording-level and (with ``time_resolution``) segment-based counts of a RecordingDetector's stitched lists against
     annotations, at every threshold of ``event_decoder`` (a utilities.predictions.EventDecoder: its labels, its K thresholds, its
     fusion strategies).  int64 counters on the device: ev / tag [n_fusion, K, C, 3], seg [n_fusion, K, C, 3], sdi [n_fusion, K, 3].
@@ -136,42 +86,13 @@ class RecordingMetrics(object):
         if self.time_resolution is not None:
             self.seg = torch.zeros(shape, dtype=torch.int64, device=self.device)
             self.sdi = torch.zeros((len(self.fusion), self.K, 3), dtype=torch.int64, device=self.device)
-        self.host, self.table = None, None
-        self._status, self._up = [], {}
+        self._status, self._up = [], Uploads(self.device)
+        self._bind(RecordingReference(self.labels, self.device))
 
     # ------------------------------------------------------------------------------------------------------------------------
-    def set_reference(self, reference):
-        """reference: {filename: [(label, onset, offset), ...]} - label a class name or index, times in seconds from the start of the
-        recording; a filename that is absent is not evaluated, one with an empty list is.  Sorts, builds the CSR table and uploads it
-        once; the counters are not touched."""
-        self.host = reference_table(reference, self.labels, segments=self.time_resolution is not None)
-        h = self.host
-        pad = lambda a: a if a.size else np.zeros(1, a.dtype)
-        self.table = {'off': torch.from_numpy(h['off']).to(self.device), 'on': torch.from_numpy(pad(h['on'])).to(self.device),
-                      'end': torch.from_numpy(pad(h['end'])).to(self.device), 'n_rec': len(h['names']), 'n_events': int(h['on'].size)}
-        return self
-
-    def recording_index(self, filenames):
-        """the recordings' indices in the reference table as host int32 [R] (-1: not in the reference, not evaluated)"""
-        return np.asarray([self.host['index'].get(f, -1) for f in filenames], np.int32)
-
-    def _upload(self, name, host):
-        ring = self._up.get(name)
-        if ring is None:
-            ring = self._up[name] = PinnedRing(self.device)
-        host = np.ascontiguousarray(host, np.int32)
-        return ring.upload(host.view(np.uint8).reshape(-1))[:host.nbytes].view(torch.int32)
-
     def counters(self):
         """every device counter tensor: [ev, tag] (+ [seg, sdi] with segment-based scores)"""
         return [t for t in (self.ev, self.tag, self.seg, self.sdi) if t is not None]
-
-    def reset(self):
-        """zero the counters and forget the statuses (start of an evaluation)"""
-        for t in self.counters():
-            t.zero_()
-        self._status = []
-        return self
 
     def update(self, stitched, cap, filenames, durations=None):
         """one detector call: ``stitched`` {at_m: (count, out, status)} and ``cap`` as ``RecordingDetector.stitch`` returns them,
@@ -187,15 +108,11 @@ class RecordingMetrics(object):
             if durations is None or len(durations) != len(filenames):
                 raise ValueError('RecordingMetrics.update: segment-based counts need the recordings\' durations, one per recording')
             words = [segment_words(d, self.host['max_end'][i] if i >= 0 else 0.0, self.time_resolution) for d, i in zip(durations, idx)]
-        for m in self.fusion:
-            count = stitched[m][0]
-            if tuple(count.shape) != (self.K, len(filenames), self.C):
-                raise ValueError(f'RecordingMetrics.update: counts {tuple(count.shape)} for {self.K} thresholds x {len(filenames)} '
-                                 f'recordings x {self.C} classes')
+        self._check_counts(stitched, len(filenames))
         if not filenames:
             return
-        d_idx = self._upload('idx', idx)
-        d_words = None if words is None else self._upload('words', words)
+        d_idx = self._up('idx', idx)
+        d_words = None if words is None else self._up('words', np.asarray(words, np.int32))
         thresholds = [operating_point(t) for t in self.decoder.threshold_values]
         for i, m in enumerate(self.fusion):
             count, out, st = stitched[m]
@@ -207,37 +124,16 @@ class RecordingMetrics(object):
                                                  time_resolution=self.time_resolution)
                 self._status.append((s, filenames, thresholds, f'recording_segment_counts (fusion {m})'))
 
-    def _read(self):
-        """counters (in the order of counters()) and statuses as numpy, from ONE device->host copy"""
-        ts = self.counters() + [s[0].to(torch.int64) for s in self._status]
-        h = torch.cat([t.reshape(-1) for t in ts]).cpu().numpy()
-        got, o = [], 0
-        for t in ts:
-            got.append(h[o:o + t.numel()].reshape(t.shape))
-            o += t.numel()
-        n = len(self.counters())
-        return got[:n], got[n:]
-
-    def _checked(self):
-        counters, statuses = self._read()
-        for st, (_, filenames, thresholds, what) in zip(statuses, self._status):
-            err = status_error(st, filenames, thresholds, what)
-            if err is not None:
-                raise err
-        return counters
-
     def counts(self):
         """(ev [n_fusion, K, C, 3] {tp, n_ref, n_sys}, tag [n_fusion, K, C, 3] {tp, fp, fn}) as numpy int64; one device->host copy;
         raises on a status"""
-        got = self._checked()
-        return got[0], got[1]
+        return tuple(self._checked()[:2])
 
     def segment_counts(self):
         """(seg [n_fusion, K, C, 3] {tp, n_ref, n_sys}, sdi [n_fusion, K, 3] {S, D, I}) as numpy int64, None without time_resolution"""
         if self.seg is None:
             return None
-        got = self._checked()
-        return got[2], got[3]
+        return tuple(self._checked()[2:])
 
     def compute(self):
         """{at_m: [per threshold {'f1', 'precision', 'recall', 'class_wise', 'clip': {...}[, 'segment': {...}]}]}: what

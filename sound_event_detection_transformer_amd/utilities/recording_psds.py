@@ -40,36 +40,11 @@ import torch
 
 from .. import ops
 from .predictions import operating_point
-from .psds import SETTINGS, PsdsResult, _curve, _rates
-from .recording_metrics import reference_table, status_error
-from .transforms import PinnedRing
+from .psds import SETTINGS, finish
+from .scoring import RecordingReference, RecordingScorer, Uploads, prefix_max, reference_constants    # noqa: F401 (importers)
 
 
-def prefix_max(end, off):
-    """per (recording, class) list of the CSR table (``off`` [N * C + 1], ``end`` [E]) the running maximum of ``end``: float64 [E].
-    No reference before the first j of a list with prefix_max[j] > t ends after t."""
-    out = np.array(end, np.float64)
-    for a, b in zip(off[:-1], off[1:]):
-        if b > a:
-            out[a:b] = np.maximum.accumulate(out[a:b])
-    return out
-
-
-def reference_constants(host, n_classes):
-    """per reference recording of the table: (n [N, C] int64 the number, t [N, C] float64 the summed duration) of every class's
-    reference events, zero-length ones left out"""
-    N = len(host['names'])
-    n, t = np.zeros((N, n_classes), np.int64), np.zeros((N, n_classes), np.float64)
-    dur = host['end'] - host['on']
-    for i in range(N):
-        for c in range(n_classes):
-            d = dur[host['off'][i * n_classes + c]:host['off'][i * n_classes + c + 1]]
-            d = d[d > 0]
-            n[i, c], t[i, c] = d.size, d.sum()
-    return n, t
-
-
-class RecordingPsds(object):
+class RecordingPsds(RecordingScorer):
     """PSDS of a RecordingDetector's stitched lists against annotations, accumulated on the device at every threshold of
     ``event_decoder`` (a utilities.predictions.EventDecoder: its labels, its K thresholds - one operating point each - and its fusion
     strategies).  int64 counters [n_fusion, K, C, C + 1] on the device, PsdsMetrics' layout.  The dataset constants n_c, T_c and T
@@ -83,45 +58,25 @@ class RecordingPsds(object):
         if any(math.isnan(t) for t in (self.dtc, self.gtc, self.cttc)):
             raise ValueError('RecordingPsds: a tolerance criterion is NaN')
         self.counts = torch.zeros((len(self.fusion), self.K, self.C, self.C + 1), dtype=torch.int64, device=self.device)
-        self.host, self.table, self._rec_n, self._rec_t = None, None, None, None
-        self._status, self._up, self._pass = [], {}, None
+        self._status, self._up = [], Uploads(self.device)
+        self._bind(RecordingReference(self.labels, self.device))
+        self._pass = None
         self._zero_constants()
+
+    # the launch also reads 'pmax', the running maximum of the ends: built when the table is first asked for
+    table = property(lambda self: self.reference.table and self.reference.with_pmax())
 
     def _zero_constants(self):
         self.n_gt, self.gt_dur, self.total_dur = np.zeros(self.C, np.int64), np.zeros(self.C, np.float64), 0.0
 
     # ------------------------------------------------------------------------------------------------------------------------
-    def set_reference(self, reference):
-        """reference: {filename: [(label, onset, offset), ...]} as RecordingMetrics.set_reference takes it.  Sorts, builds the CSR table
-        and the prefix maximum of the ends, and uploads them once; neither the counters nor the constants are touched."""
-        self.host = h = reference_table(reference, self.labels)
-        self._rec_n, self._rec_t = reference_constants(h, self.C)
-        pad = lambda a: a if a.size else np.zeros(1, a.dtype)
-        up = lambda a: torch.from_numpy(pad(a)).to(self.device)
-        self.table = {'off': torch.from_numpy(h['off']).to(self.device), 'on': up(h['on']), 'end': up(h['end']),
-                      'pmax': up(prefix_max(h['end'], h['off'])), 'n_rec': len(h['names']), 'n_events': int(h['on'].size)}
-        return self
-
-    def recording_index(self, filenames):
-        """the recordings' indices in the reference table as host int32 [R] (-1: not in the reference, not evaluated)"""
-        return np.asarray([self.host['index'].get(f, -1) for f in filenames], np.int32)
-
-    def _upload(self, name, host, dtype):
-        ring = self._up.get(name)
-        if ring is None:
-            ring = self._up[name] = PinnedRing(self.device)
-        host = np.ascontiguousarray(host)
-        return ring.upload(host.view(np.uint8).reshape(-1))[:host.nbytes].view(dtype)
-
     def counters(self):
         return [self.counts]
 
     def reset(self):
         """zero the counters and the dataset constants and forget the statuses (start of an evaluation)"""
-        self.counts.zero_()
         self._zero_constants()
-        self._status = []
-        return self
+        return RecordingScorer.reset(self)
 
     def _durations(self, filenames, durations):
         if self.table is None:
@@ -138,10 +93,11 @@ class RecordingPsds(object):
         and returns (rec_idx int32 [R], durations float64 [R]) as the launch takes them"""
         durations = self._durations(filenames, durations)
         idx = self.recording_index(filenames)
+        rec_n, rec_t = self.reference.constants()
         for i, d in zip(idx, durations):
             if i >= 0:
-                self.n_gt += self._rec_n[i]
-                self.gt_dur += self._rec_t[i]
+                self.n_gt += rec_n[i]
+                self.gt_dur += rec_t[i]
                 self.total_dur += float(d)
         return idx, durations
 
@@ -152,16 +108,12 @@ class RecordingPsds(object):
         compute().  n_c, T_c and T grow by the call's recordings that are in the reference (``account``)."""
         filenames = list(filenames)
         self._durations(filenames, durations)
-        for m in self.fusion:
-            count = stitched[m][0]
-            if tuple(count.shape) != (self.K, len(filenames), self.C):
-                raise ValueError(f'RecordingPsds.update: counts {tuple(count.shape)} for {self.K} thresholds x {len(filenames)} '
-                                 f'recordings x {self.C} classes')
+        self._check_counts(stitched, len(filenames))
         idx, durations = self.account(filenames, durations)
         if not filenames:
             return
-        d_idx = self._upload('idx', idx, torch.int32)
-        d_dur = self._upload('dur', durations, torch.float64)
+        d_idx = self._up('idx', idx)
+        d_dur = self._up('dur', durations)
         words = self.K * len(filenames) * self.C * ((int(cap) + 63) // 64)
         if self._pass is None or self._pass.numel() < words:
             self._pass = torch.empty(words, dtype=torch.int64, device=self.device)
@@ -175,28 +127,14 @@ class RecordingPsds(object):
     def counts_host(self):
         """counts [n_fusion, K, C, C + 1] as numpy int64, from ONE device->host copy of counters and statuses; raises on a status,
         naming recording, threshold and reason"""
-        ts = [self.counts] + [s[0].to(torch.int64) for s in self._status]
-        h = torch.cat([t.reshape(-1) for t in ts]).cpu().numpy()
-        o = self.counts.numel()
-        for s, filenames, thresholds, what in self._status:
-            err = status_error(h[o:o + s.numel()].reshape(s.shape), filenames, thresholds, what)
-            if err is not None:
-                raise err
-            o += s.numel()
-        return h[:self.counts.numel()].reshape(self.counts.shape)
+        return self._checked()[0]
 
     def compute(self, settings=SETTINGS):
         """{at_m: PsdsResult}: per fusion strategy the PSD scores at ``settings`` ((alpha_ct, alpha_st, max_efpr) triples), the rates
-        they come from and the decoder's thresholds - PsdsMetrics.compute's result, finished by the same functions (psds._rates,
-        psds._curve) from the constants accumulated since reset()"""
+        they come from and the decoder's thresholds - PsdsMetrics.compute's result, finished by the same function (psds.finish)
+        from the constants accumulated since reset()"""
         if self.table is None:
             raise RuntimeError('RecordingPsds.compute: set_reference() first')
         counts = self.counts_host()
-        res = {}
-        for i, m in enumerate(self.fusion):
-            tpr, fpr, ctr, valid = _rates(counts[i], self.n_gt, self.gt_dur, self.total_dur)
-            r = PsdsResult(psds={tuple(s): _curve(tpr, fpr, ctr, valid, *s)[0] for s in settings}, tpr=tpr, fpr=fpr, ctr=ctr,
-                           thresholds=self.decoder.operating_points())
-            r._valid = valid
-            res[m] = r
-        return res
+        return {m: finish(counts[i], self.n_gt, self.gt_dur, self.total_dur, settings, self.decoder.operating_points())
+                for i, m in enumerate(self.fusion)}
