@@ -45,8 +45,9 @@ def _dev_env(name, default):
 IGEMM_BREG = _dev_env('SEDT_IGEMM_BREG', '0') != '0'   # developer A/B switch (csrc/igemm3.hip, BR = 1): weights through registers out of their fragment-major images
 RELU_BITS = _dev_env('SEDT_RELU_BITS', '1') != '0'      # developer A/B switch: 0 = the backward masks with the bf16 activations
 PROFILE = None   # bench.py sets this to a list: every GEMM launch then also records (argument block, dtype, shape, operands, hint)
+# hint (igemm's argument): how the un-recorded step launches the problem being recorded - 'conv3x3_c64_kernel' (direct kernel), ('group', kernel
+# label, share of the recorded problem's flops the grouped form executes), 'wgrad_group'; None: as recorded
 PROFILE_FUSED = []     # with PROFILE on: (kernel-name prefix, algorithmic flop, algorithmic bytes) of every fused-Bottleneck launch of the recorded step
-PROFILE_HINT = None   # how the un-profiled step launches the problem being recorded: 'conv3x3_c64_kernel' (direct kernel), ('group', kernel label, share of the recorded problem's flops the grouped form executes)
 
 
 def _dev_check(*ts):
@@ -332,7 +333,19 @@ def _describe(a, code, njobs=0):
     return buf.value.decode() if r == 0 else None
 
 
-def _igemm_x3_fast(M, N, K, A, lda, B, ldb, Cout, ldc, kw):
+def _launch_igemm(a, code, shape, kept, hint, x3=False):
+    """the tail of every single-GEMM launch: record it (the operand tensors `kept` alive, so that the launch can be replayed for timing), count
+    the kernel instance the dispatcher picks in the launch log (lib.launch_log()), launch"""
+    if PROFILE is not None:
+        PROFILE.append((a, code, shape, kept, hint))
+    if L.LAUNCH_LOG is not None:
+        name = _describe(a, code)
+        if name is not None:
+            L.LAUNCH_LOG['igemm_x3:' + name if x3 else 'igemm:' + name.split('(')[0]] += 1
+    L.check(L.load().sedt_igemm(C.byref(a), code, L.stream_ptr()), 'sedt_igemm_x3' if x3 else 'sedt_igemm')
+
+
+def _igemm_x3_fast(M, N, K, A, lda, B, ldb, Cout, ldc, kw, hint):
     conv = kw.get('conv')
     Ci = conv[2] if conv is not None else K
     rows = _x3_rows(M, conv)
@@ -354,19 +367,13 @@ def _igemm_x3_fast(M, N, K, A, lda, B, ldb, Cout, ldc, kw):
         X3_CACHE[(Cout.data_ptr(), M, N, ldc)] = (Cout, img, Cout._version)
     else:
         X3_CACHE.pop((Cout.data_ptr(), M, N, ldc), None)          # (rewritten without a new image: a cached one would be stale)
-    if PROFILE is not None:
-        PROFILE.append((a, BF16, (M, N, 3 * K, 0, 0 if conv is None else 1), (A, B, Cout, kw, A3, B3), PROFILE_HINT))
-    if L.LAUNCH_LOG is not None:
-        name = _describe(a, BF16)
-        if name is not None:
-            L.LAUNCH_LOG['igemm_x3:' + name] += 1
-    L.check(L.load().sedt_igemm(C.byref(a), BF16, L.stream_ptr()), 'sedt_igemm_x3')
+    _launch_igemm(a, BF16, (M, N, 3 * K, 0, 0 if conv is None else 1), (A, B, Cout, kw, A3, B3), hint, x3=True)
 
 
-def igemm(dtype, M, N, K, A, lda, B, ldb, Cout, ldc, **kw):
-    """raw implicit GEMM call (arguments as igemm_args)"""
+def igemm(dtype, M, N, K, A, lda, B, ldb, Cout, ldc, hint=None, **kw):
+    """raw implicit GEMM call (arguments as igemm_args); hint: what a recording notes beside the problem (PROFILE)"""
     if dtype == F32 and L.GEMM_X3 and _x3_fast_ok(M, N, K, A, lda, B, ldb, Cout, ldc, kw):
-        return _igemm_x3_fast(M, N, K, A, lda, B, ldb, Cout, ldc, kw)
+        return _igemm_x3_fast(M, N, K, A, lda, B, ldb, Cout, ldc, kw, hint)
     if dtype == F32 and L.GEMM_X3 and Cout is not None and X3_CACHE:
         X3_CACHE.pop((Cout.data_ptr(), M, N, ldc), None)          # the generic kernel rewrites Cout and leaves no operand image
     a = igemm_args(M, N, K, A, lda, B, ldb, Cout, ldc, **kw)
@@ -386,13 +393,7 @@ def igemm(dtype, M, N, K, A, lda, B, ldb, Cout, ldc, **kw):
         if not taken.value:
             POOL.give_back(riders)
         return
-    if PROFILE is not None:     # the operand tensors are kept alive so that the launch can be replayed for timing
-        PROFILE.append((a, L.gemm_dtype(dtype), (M, N, K, trans, 0 if conv is None else 1), (A, B, Cout, kw), PROFILE_HINT))
-    if L.LAUNCH_LOG is not None:     # (lib.launch_log(): also which kernel instance the dispatcher picks for this problem)
-        name = _describe(a, L.gemm_dtype(dtype))
-        if name is not None:
-            L.LAUNCH_LOG['igemm:' + name.split('(')[0]] += 1
-    L.check(L.load().sedt_igemm(C.byref(a), L.gemm_dtype(dtype), L.stream_ptr()), 'sedt_igemm')
+    _launch_igemm(a, L.gemm_dtype(dtype), (M, N, K, trans, 0 if conv is None else 1), (A, B, Cout, kw), hint)
 
 
 def _geom_tuple(g, transposed=False):
@@ -481,192 +482,183 @@ def linear_group(dtype, items):
         outs.append(out)
         args.append(((M, N, K, x, x.stride(0), w, w.stride(0), out, out.stride(0)), dict(out_f32=int(out_f32), **kw)))
     if len(args) == 1 or PROFILE is not None or (_co['on'] and POOL.gemms) or (dtype == F32 and L.GEMM_X3 and X3_FAST):
-        global PROFILE_HINT
+        hint = None
         if len(args) > 1 and PROFILE is not None and dtype == BF16:
-            PROFILE_HINT = ('group', _group_label([igemm_args(*a, **kw) for a, kw in args]), 1.0)
+            hint = ('group', _group_label([igemm_args(*a, **kw) for a, kw in args]), 1.0)
         for a, kw in args:
-            igemm(dtype, *a, **kw)
-        PROFILE_HINT = None
+            igemm(dtype, *a, hint=hint, **kw)
         return outs
     arr = (L.SedtIgemm * len(args))(*[igemm_args(*a, **kw) for a, kw in args])
     L.check(L.load().sedt_igemm_group(arr, len(args), L.gemm_dtype(dtype), L.stream_ptr()), 'igemm_group')
     return outs
 
 
-def _conv3_c64_ok(dtype, t, g, ep, out, profiling_ok=False):
-    """envelope of the direct 3x3 kernel (csrc/conv3x3_c64.hip): the layer1 conv2 geometry, plain epilogues"""
-    return (CONV3_DIRECT and (PROFILE is None or profiling_ok) and dtype == BF16 and g.Ci == 64 and g.Co == 64 and g.KH == 3 and g.KW == 3
+# ---- the launch form of a convolution.  conv_fwd / conv_dgrad run every backbone convolution that is not a fused Bottleneck; three special
+# forms stand beside the generic implicit GEMM.  conv_form decides, the envelopes below say when a form applies, CONV_FORMS holds the
+# precedence.  A recording (PROFILE) launches the generic kernel whatever the plan and notes the planned form as the entry's hint.
+#
+# s2_parity: the input gradient of a stride-2 3x3 convolution (layer2 / layer3 block 0) by OUTPUT PARITY.  The transposed gather of the plain
+# form walks all nine taps for every input pixel, but a pixel (hi, wi) only ever receives taps with kh = hi + 1 and kw = wi + 1 (mod 2): three
+# of four (tap, pixel) pairs multiply rows of zeros.  Split by the parity of (hi, wi) the problem is four small REGULAR convolutions over dY -
+# 1, 2, 2 and 4 taps - whose outputs interleave in dx: one grouped launch (sedt_igemm_group) of four problems that read their tap blocks of
+# the packed dgrad weight in place (SedtIgemm.btap) and write every second row / column of dx (SedtIgemm.omap), epilogue operands (residual,
+# ReLU mask bits) indexed by the dx pixel.  A quarter of the MFMAs, the same sums in the same order.
+#
+# dil_halves: layer4's dilated 3x3 convolutions (dilation 2, padding 2) run on a map of FOUR columns: the left tap column (kw = 0) lands inside
+# the image only for output columns 2, 3 and the right one (kw = 2) only for columns 0, 1 - a third of the tap walk multiplies zero rows.
+# Split by column half, each half is a regular 3 x 2-tap convolution over all four input columns with its own six tap blocks of the packed
+# weight (btap) and its own two output columns (omap): two problems of 128 tiles of 128x128 in ONE grouped ping-pong launch
+# (igemm3_w8_group_kernel), 2/3 of the K loop each.  Forward and input gradient (the mirror image) alike.
+#
+# Both grouped forms run in bf16 and in the fast bf16x3 form of the f32 mode (split operand images, f32 epilogue).
+S2_PARITY = _dev_env('SEDT_S2_PARITY', '1') != '0'
+DIL_HALVES = _dev_env('SEDT_DIL_HALVES', '1') != '0'
+
+
+def _direct3x3_ok(kind, dtype, t, g, w, out, ep):
+    """envelope of the direct 3x3 kernel (csrc/conv3x3_c64.hip): the layer1 conv2 geometry, plain epilogues.  The input gradient of a
+    stride-1 3x3 conv is the same conv, taps flipped: the kernel takes it when no per-channel scale / bias is asked for"""
+    return (CONV3_DIRECT and dtype == BF16 and g.Ci == 64 and g.Co == 64 and g.KH == 3 and g.KW == 3
             and g.sh == 1 and g.sw == 1 and g.ph == 1 and g.pw == 1 and g.dh == 1 and g.dw == 1 and g.Wi == 16
             and t.stride(0) == 64 and out.stride(0) == 64 and set(ep) <= {'scale', 'bias', 'act', 'mask', 'ldm', 'tile'}
             and ep.get('act', 0) in (0, ACT_RELU) and tuple(ep.get('tile', (0, 0))) == (0, 0)
-            and (ep.get('mask') is None or (ep.get('ldm', 64) == 64 and ep.get('act', 0) == 0)))
+            and (ep.get('mask') is None or (ep.get('ldm', 64) == 64 and ep.get('act', 0) == 0))
+            and (kind == 'fwd' or ('scale' not in ep and 'bias' not in ep)))
 
 
-def _conv3_c64(t, B, g, w, flip, out, ep):
-    L.check(L.load().sedt_conv3x3_c64(_p(t), _p(w), flip, _p(ep.get('scale')), _p(ep.get('bias')), 1 if ep.get('act', 0) == ACT_RELU else 0,
-                                      _p(ep.get('mask')), _p(out), B, g.Hi, g.Wi, 64, L.stream_ptr()), 'conv3x3_c64')
+def _grouped_ok(dtype, t, out, ep):
+    """what both grouped forms ask: no co-scheduled riders; bf16, or the fast bf16x3 form of the f32 mode on f32 operands whose images the
+    split kernel can make (16-byte aligned rows).  A grouped form that passes runs on split operands (x3) exactly when dtype is F32"""
+    x3 = dtype == F32 and L.GEMM_X3 and X3_FAST
+    if _co['on'] or not (dtype == BF16 or x3):
+        return False
+    return not x3 or (t.dtype == torch.float32 and out.dtype == torch.float32 and t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0
+                      and (ep.get('res') is None or ep['res'].dtype == torch.float32)
+                      and (ep.get('mask') is None or ep.get('mask_bits') or ep['mask'].dtype == torch.float32))
+
+
+def _s2_parity_ok(kind, dtype, dy, g, wb, out, ep):
+    return (S2_PARITY and kind == 'dgrad' and _grouped_ok(dtype, dy, out, ep) and g.KH == 3 and g.KW == 3 and g.sh == 2 and g.sw == 2
+            and g.ph == 1 and g.pw == 1 and g.dh == 1 and g.dw == 1 and g.Co % 64 == 0 and g.Ci % 8 == 0 and wb.stride(0) == 9 * g.Co
+            and dy.stride(0) % 8 == 0 and out.stride(0) % 8 == 0 and set(ep) <= {'mask', 'ldm', 'mask_bits', 'res', 'ldr', 'alpha'})
+
+
+def _dil_halves_ok(kind, dtype, t, g, w, out, ep):
+    d = g.dh
+    cin, cout = (g.Co, g.Ci) if kind == 'dgrad' else (g.Ci, g.Co)          # channels of the gathered tensor / of the output
+    return (DIL_HALVES and _grouped_ok(dtype, t, out, ep) and g.KH == 3 and g.KW == 3 and g.sh == 1 and g.sw == 1 and g.dw == d and d >= 1
+            and g.ph == d and g.pw == d and g.Wi == 2 * d and g.Wo == g.Wi and g.Ho == g.Hi and cin % 64 == 0 and cout % 128 == 0
+            and w.stride(0) == 9 * cin and t.stride(0) % 8 == 0 and out.stride(0) % 8 == 0
+            and set(ep) <= {'scale', 'bias', 'act', 'mask', 'ldm', 'mask_bits', 'res', 'ldr', 'alpha', 'bits_out', 'act_post_res'}
+            and (t.shape[0] // 2 // 128) * (cout // 128) >= 96)         # (the halves pay while the two problems fill the chip with 128x128 tiles)
+
+
+# form -> (envelope, share of the nine-tap walk the form executes); a new form is added here and, by kind and in order of precedence, below
+_FORMS = {'direct3x3': (_direct3x3_ok, 1.0), 's2_parity': (_s2_parity_ok, 0.25), 'dil_halves': (_dil_halves_ok, 2.0 / 3.0)}
+CONV_FORMS = {'fwd': ('direct3x3', 'dil_halves'), 'dgrad': ('s2_parity', 'dil_halves', 'direct3x3')}
+
+
+def conv_form(kind, dtype, t, g, w, out, ep):
+    """(form, x3, share) of the convolution conv_fwd (kind 'fwd', t = x) / conv_dgrad ('dgrad', t = dY) is asked for: the first form of
+    CONV_FORMS[kind] whose envelope holds, else 'gemm'; whether the form runs on split operand images; the share of the tap walk it executes.
+    Reads the geometry, the epilogue and the operands' dtype / address / strides / rows, and the switches as they stand at the call"""
+    for form in CONV_FORMS[kind]:
+        ok, share = _FORMS[form]
+        if ok(kind, dtype, t, g, w, out, ep):
+            return form, form != 'direct3x3' and dtype == F32, share
+    return 'gemm', False, 1.0
+
+
+def _s2_parity_subs(B, g, C_):
+    for ph_ in (0, 1):                                   # parity of the input row hi = 2a + ph_
+        nh, khs = (g.Hi + 1 - ph_) // 2, ([1] if ph_ == 0 else [0, 2])
+        for pw_ in (0, 1):
+            nw, kws = (g.Wi + 1 - pw_) // 2, ([1] if pw_ == 0 else [0, 2])
+            if nh and nw:
+                # a "transposed" stride-1 gather over the dY grid: tap (i, j) of the walk reads dY[a + ph_ - i][b + pw_ - j], i.e. the original
+                # taps in ascending (kh, kw) order - rows / columns beyond the grid are masked by the kernel
+                yield (B * nh * nw, (g.Ho, g.Wo, C_, nh, nw, len(khs), len(kws), 1, 1, ph_, pw_, 1, 1), (64, 64), (g.Hi, g.Wi, 2, 2, ph_, pw_),
+                       [kh * 3 + kw for kh in khs for kw in kws])
+
+
+def _dil_halves_subs(B, g, C_, transposed):
+    d = g.dh
+    for half in (0, 1):
+        # forward: output columns [0, d) see taps kw in {1, 2}, columns [d, 2d) taps {0, 1}; the input gradient mirrors it
+        kw0 = (1 - half) if not transposed else half
+        yield (B * g.Ho * d, (g.Hi, g.Wi, C_, g.Ho, d, 3, 2, 1, 1, d, (d if transposed else 0), d, d), (128, 128), (g.Ho, g.Wo, 1, 1, 0, half * d),
+               [kh * 3 + kw0 + j for kh in range(3) for j in range(2)])
+
+
+def conv_group_jobs(form, kind, t, B, g, w, out, ep, x3):
+    """the argument blocks of a grouped form ('s2_parity': four problems, 'dil_halves': two), nothing is launched: each a regular
+    convolution (rows, geometry, tile, omap = (o_Hi, o_Wi, o_sh, o_sw, o_h0, o_w0), taps of the packed weight [cout][9][cin] it walks)"""
+    transposed = kind == 'dgrad'
+    cin, cout = (g.Co, g.Ci) if transposed else (g.Ci, g.Co)
+    C_ = cin
+    if x3:                          # operand images: t [pixels][2 cin] = [hi | lo], the weight [cout][9][3 cin] = [hi | hi | lo] per tap
+        t, w = _split3([(t, 0, B * (g.Ho * g.Wo if transposed else g.Hi * g.Wi), cin, t.stride(0), 0), (w, 0, cout * 9, cin, cin, 1)])
+        w = w.view(cout, 27 * cin)
+        C_ = 3 * cin
+    jobs = []
+    for M, conv, tile, omap, taps in (_s2_parity_subs(B, g, C_) if form == 's2_parity' else _dil_halves_subs(B, g, C_, transposed)):
+        a = igemm_args(M, cout, len(taps) * C_, t, t.stride(0), w, w.stride(0), out, out.stride(0), conv=conv, transposed=int(transposed),
+                       tile=tile, out_f32=int(x3), **ep)
+        a.omap, (a.o_Hi, a.o_Wi, a.o_sh, a.o_sw, a.o_h0, a.o_w0) = 1, omap
+        a.btap_on, a.f32ep, a.awrap = 1, int(x3), (cin if x3 else 0)
+        for i, tap in enumerate(taps):
+            a.btap[i] = tap * C_
+        jobs.append(a)
+    return jobs
+
+
+def conv_hint(kind, plan, t, B, g, w, out, ep):
+    """what a recording notes beside the nine-tap problem it runs in place of the planned form: the direct kernel, or the kernel the grouped
+    launch of the form's problems runs on and the share of the recorded flops it executes (bf16 only); None: nothing to note"""
+    form, x3, share = plan
+    if form == 'direct3x3':
+        return 'conv3x3_c64_kernel'
+    if form == 'gemm' or x3:
+        return None
+    return ('group', _group_label(conv_group_jobs(form, kind, t, B, g, w, out, ep, False)), share)
+
+
+def _conv(kind, dtype, t, B, g, w, out, ep):
+    """conv_fwd / conv_dgrad: plan, launch the planned form - or, under a recording, the generic GEMM with the plan as its hint"""
+    plan = conv_form(kind, dtype, t, g, w, out, ep)
+    form, x3, _ = plan
+    if PROFILE is None and form == 'direct3x3':
+        L.check(L.load().sedt_conv3x3_c64(_p(t), _p(w), int(kind == 'dgrad'), _p(ep.get('scale')), _p(ep.get('bias')),
+                                          1 if ep.get('act', 0) == ACT_RELU else 0, _p(ep.get('mask')), _p(out), B, g.Hi, g.Wi, 64,
+                                          L.stream_ptr()), 'conv3x3_c64')
+    elif PROFILE is None and form != 'gemm':
+        jobs = conv_group_jobs(form, kind, t, B, g, w, out, ep, x3)
+        L.check(L.load().sedt_igemm_group((L.SedtIgemm * len(jobs))(*jobs), len(jobs), BF16, L.stream_ptr()),
+                'igemm_group_s2' if form == 's2_parity' else 'igemm_group_dil')
+    else:
+        dgrad = kind == 'dgrad'
+        if L.LAUNCH_LOG is not None and dgrad and not g.plain:          # (a transposed gather on the general path: which geometry)
+            L.LAUNCH_LOG['conv_dgrad_gather:k%ds%d' % (g.KH, g.sh)] += 1
+        M, N, K = (B * g.Hi * g.Wi, g.Ci, g.taps * g.Co) if dgrad else (B * g.Ho * g.Wo, g.Co, g.taps * g.Ci)
+        hint = conv_hint(kind, plan, t, B, g, w, out, ep) if PROFILE is not None else None
+        if dgrad:
+            ep = dict(ep, transposed=0 if g.plain else 1)
+        igemm(dtype, M, N, K, t, t.stride(0), w, K, out, out.stride(0), conv=None if g.plain else _geom_tuple(g, dgrad), hint=hint, **ep)
     return out
 
 
 def conv_fwd(dtype, x, B, g, wf, out=None, **ep):
     """NHWC conv forward: x [B*Hi*Wi, Ci] (row stride = x.stride(0)), wf packed [Co][taps][Ci]"""
-    M = B * g.Ho * g.Wo
     if out is None:
-        out = torch.empty((M, g.Co), device=x.device, dtype=TORCH_DTYPE[dtype])
-    if _conv3_c64_ok(dtype, x, g, ep, out):
-        return _conv3_c64(x, B, g, wf, 0, out, ep)
-    if _dil_halves_ok(dtype, x, g, wf, out, ep, False):
-        return _conv_dil_halves(x, B, g, wf, out, ep, False, dtype == F32)
-    conv = None if g.plain else _geom_tuple(g)
-    global PROFILE_HINT
-    if PROFILE is not None and _conv3_c64_ok(dtype, x, g, ep, out, True):
-        PROFILE_HINT = 'conv3x3_c64_kernel'
-    elif PROFILE is not None and dtype == BF16 and _dil_halves_ok(dtype, x, g, wf, out, ep, False, True):
-        # the un-recorded step runs this conv as two column halves in one grouped launch, 6 of the 9 taps each (2/3 of the flops)
-        PROFILE_HINT = ('group', _conv_dil_halves(x, B, g, wf, out, ep, False, False, describe=True), 2.0 / 3.0)
-    igemm(dtype, M, g.Co, g.taps * g.Ci, x, x.stride(0), wf, g.taps * g.Ci, out, out.stride(0), conv=conv, **ep)
-    PROFILE_HINT = None
-    return out
-
-
-# The input gradient of a stride-2 3x3 convolution (layer2 / layer3 block 0) by OUTPUT PARITY.  The transposed gather of the plain form walks
-# all nine taps for every input pixel, but a pixel (hi, wi) only ever receives taps with kh = hi + 1 and kw = wi + 1 (mod 2): three of four
-# (tap, pixel) pairs multiply rows of zeros.  Split by the parity of (hi, wi) the problem is four small REGULAR convolutions over dY - 1, 2,
-# 2 and 4 taps - whose outputs interleave in dx: one grouped launch (sedt_igemm_group) of four problems that read their tap blocks of the
-# packed dgrad weight in place (SedtIgemm.btap) and write every second row / column of dx (SedtIgemm.omap), epilogue operands (residual,
-# ReLU mask bits) indexed by the dx pixel.  A quarter of the MFMAs, the same sums in the same order.
-S2_PARITY = _dev_env('SEDT_S2_PARITY', '1') != '0'
-
-
-def _dgrad_s2_ok(dtype, dy, g, wb, out, ep, profiling_ok=False):
-    """bf16, or the fast bf16x3 form of the f32 mode (split operand images, f32 epilogue)"""
-    x3 = dtype == F32 and L.GEMM_X3 and X3_FAST
-    if not (dtype == BF16 or x3):
-        return False
-    if x3 and not (dy.dtype == torch.float32 and out.dtype == torch.float32 and dy.data_ptr() % 16 == 0 and dy.stride(0) % 4 == 0
-                   and (ep.get('res') is None or ep['res'].dtype == torch.float32)
-                   and (ep.get('mask') is None or ep.get('mask_bits') or ep['mask'].dtype == torch.float32)):
-        return False
-    return (S2_PARITY and (PROFILE is None or profiling_ok) and not _co['on'] and g.KH == 3 and g.KW == 3 and g.sh == 2 and g.sw == 2
-            and g.ph == 1 and g.pw == 1 and g.dh == 1 and g.dw == 1 and g.Co % 64 == 0 and g.Ci % 8 == 0 and wb.stride(0) == 9 * g.Co
-            and dy.stride(0) % 8 == 0 and out.stride(0) % 8 == 0 and set(ep) <= {'mask', 'ldm', 'mask_bits', 'res', 'ldr', 'alpha'})
-
-
-def _conv_dgrad_s2(dy, B, g, wb, out, ep, x3=False, describe=False):
-    """describe: build the four problems and return the label of the kernel their grouped launch runs on (nothing is launched)"""
-    Co = g.Co
-    if x3 and not describe:                                               # operand images: dY [pixels][2 Co] = [hi | lo], the weight [Ci][9][3 Co] = [hi | hi | lo] per tap
-        dy, wb = _split3([(dy, 0, B * g.Ho * g.Wo, g.Co, dy.stride(0), 0), (wb, 0, g.Ci * 9, g.Co, g.Co, 1)])
-        wb = wb.view(g.Ci, 27 * g.Co)
-        Co = 3 * g.Co
-    jobs = []
-    for ph_ in (0, 1):                                   # parity of the input row hi = 2a + ph_
-        nh, khs = (g.Hi + 1 - ph_) // 2, ([1] if ph_ == 0 else [0, 2])
-        for pw_ in (0, 1):
-            nw, kws = (g.Wi + 1 - pw_) // 2, ([1] if pw_ == 0 else [0, 2])
-            if nh == 0 or nw == 0:
-                continue
-            # a "transposed" stride-1 gather over the dY grid: tap (i, j) of the walk reads dY[a + ph_ - i][b + pw_ - j], i.e. the original
-            # taps in ascending (kh, kw) order - rows / columns beyond the grid are masked by the kernel
-            conv = (g.Ho, g.Wo, Co, nh, nw, len(khs), len(kws), 1, 1, ph_, pw_, 1, 1)
-            taps = [(kh, kw) for kh in khs for kw in kws]
-            a = igemm_args(B * nh * nw, g.Ci, len(taps) * Co, dy, dy.stride(0), wb, wb.stride(0), out, out.stride(0), conv=conv,
-                           transposed=1, tile=(64, 64), out_f32=int(x3), **ep)
-            a.omap, a.o_Hi, a.o_Wi, a.o_sh, a.o_sw, a.o_h0, a.o_w0 = 1, g.Hi, g.Wi, 2, 2, ph_, pw_
-            a.btap_on, a.f32ep, a.awrap = 1, int(x3), (g.Co if x3 else 0)
-            for t_, (kh, kw) in enumerate(taps):
-                a.btap[t_] = (kh * 3 + kw) * Co
-            jobs.append(a)
-    if describe:
-        return _group_label(jobs)
-    arr = (L.SedtIgemm * len(jobs))(*jobs)
-    L.check(L.load().sedt_igemm_group(arr, len(jobs), BF16, L.stream_ptr()), 'igemm_group_s2')
-    return out
-
-
-# layer4's dilated 3x3 convolutions (dilation 2, padding 2) run on a map of FOUR columns: the left tap column (kw = 0) lands inside the image
-# only for output columns 2, 3 and the right one (kw = 2) only for columns 0, 1 - a third of the tap walk multiplies zero rows.  Split by
-# column half, each half is a regular 3 x 2-tap convolution over all four input columns with its own six tap blocks of the packed
-# weight (SedtIgemm.btap) and its own two output columns (SedtIgemm.omap): two problems of 128 tiles of 128x128 in ONE grouped ping-pong
-# launch (igemm3_w8_group_kernel), 2/3 of the K loop each.  Forward and input gradient (the mirror image) alike.
-DIL_HALVES = _dev_env('SEDT_DIL_HALVES', '1') != '0'
-
-
-def _dil_halves_ok(dtype, t, g, w, out, ep, transposed, profiling_ok=False):
-    x3 = dtype == F32 and L.GEMM_X3 and X3_FAST
-    if not (DIL_HALVES and (dtype == BF16 or x3) and (PROFILE is None or profiling_ok) and not _co['on']):
-        return False
-    d = g.dh
-    cin, cout = (g.Co, g.Ci) if transposed else (g.Ci, g.Co)          # channels of the gathered tensor / of the output
-    if not (g.KH == 3 and g.KW == 3 and g.sh == 1 and g.sw == 1 and g.dw == d and d >= 1 and g.ph == d and g.pw == d and g.Wi == 2 * d
-            and g.Wo == g.Wi and g.Ho == g.Hi and cin % 64 == 0 and cout % 128 == 0 and w.stride(0) == 9 * cin and t.stride(0) % 8 == 0
-            and out.stride(0) % 8 == 0):
-        return False
-    if x3 and not (t.dtype == torch.float32 and out.dtype == torch.float32 and t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0
-                   and all(ep.get(k_) is None or ep[k_].dtype == torch.float32 for k_ in ('res',))
-                   and (ep.get('mask') is None or ep.get('mask_bits') or ep['mask'].dtype == torch.float32)):
-        return False
-    # (the halves pay while the two problems fill the chip with 128x128 tiles)
-    B_rows = t.shape[0]
-    return set(ep) <= {'scale', 'bias', 'act', 'mask', 'ldm', 'mask_bits', 'res', 'ldr', 'alpha', 'bits_out', 'act_post_res'} \
-        and (B_rows // 2 // 128) * (cout // 128) >= 96
-
-
-def _conv_dil_halves(t, B, g, w, out, ep, transposed, x3, describe=False):
-    """t = x (forward) or dY (input gradient); w = the packed forward / dgrad operand [cout][9][cin]"""
-    d = g.dh
-    cin, cout = (g.Co, g.Ci) if transposed else (g.Ci, g.Co)
-    C = cin
-    if x3 and not describe:
-        t, w = _split3([(t, 0, B * g.Hi * g.Wi, cin, t.stride(0), 0), (w, 0, cout * 9, cin, cin, 1)])
-        w = w.view(cout, 27 * cin)
-        C = 3 * cin
-    jobs = []
-    for half in (0, 1):
-        # forward: output columns [0, d) see taps kw in {1, 2}, columns [d, 2d) taps {0, 1}; the input gradient mirrors it
-        kw0 = (1 - half) if not transposed else half
-        conv = (g.Hi, g.Wi, C, g.Ho, d, 3, 2, 1, 1, d, (d if transposed else 0), d, d)
-        a = igemm_args(B * g.Ho * d, cout, 6 * C, t, t.stride(0), w, w.stride(0), out, out.stride(0), conv=conv, transposed=int(transposed),
-                       tile=(128, 128), out_f32=int(x3), **ep)
-        a.omap, a.o_Hi, a.o_Wi, a.o_sh, a.o_sw, a.o_h0, a.o_w0 = 1, g.Ho, g.Wo, 1, 1, 0, half * d
-        a.btap_on, a.f32ep, a.awrap = 1, int(x3), (cin if x3 else 0)
-        for kh in range(3):
-            for j in range(2):
-                a.btap[kh * 2 + j] = (kh * 3 + kw0 + j) * C
-        jobs.append(a)
-    if describe:
-        return _group_label(jobs)
-    arr = (L.SedtIgemm * 2)(*jobs)
-    L.check(L.load().sedt_igemm_group(arr, 2, BF16, L.stream_ptr()), 'igemm_group_dil')
-    return out
+        out = torch.empty((B * g.Ho * g.Wo, g.Co), device=x.device, dtype=TORCH_DTYPE[dtype])
+    return _conv('fwd', dtype, x, B, g, wf, out, ep)
 
 
 def conv_dgrad(dtype, dy, B, g, wb, out=None, **ep):
     """dx [B*Hi*Wi, Ci] = conv_transpose(dy [B*Ho*Wo, Co]); wb packed [Ci][taps][Co] (BN scale folded in)"""
-    M = B * g.Hi * g.Wi
     if out is None:
-        out = torch.empty((M, g.Ci), device=dy.device, dtype=TORCH_DTYPE[dtype])
-    if _dgrad_s2_ok(dtype, dy, g, wb, out, ep):
-        return _conv_dgrad_s2(dy, B, g, wb, out, ep, x3=dtype == F32)
-    if _dil_halves_ok(dtype, dy, g, wb, out, ep, True):
-        return _conv_dil_halves(dy, B, g, wb, out, ep, True, dtype == F32)
-    if _conv3_c64_ok(dtype, dy, g, ep, out) and 'scale' not in ep and 'bias' not in ep:
-        return _conv3_c64(dy, B, g, wb, 1, out, ep)       # the input gradient of a stride-1 3x3 conv is the same conv, taps flipped
-    conv = None if g.plain else _geom_tuple(g, transposed=True)
-    if L.LAUNCH_LOG is not None and not g.plain:          # (a transposed gather on the general path: which geometry)
-        L.LAUNCH_LOG['conv_dgrad_gather:k%ds%d' % (g.KH, g.sh)] += 1
-    global PROFILE_HINT
-    if PROFILE is not None and _conv3_c64_ok(dtype, dy, g, ep, out, True) and 'scale' not in ep and 'bias' not in ep:
-        PROFILE_HINT = 'conv3x3_c64_kernel'
-    elif PROFILE is not None and dtype == BF16 and _dgrad_s2_ok(dtype, dy, g, wb, out, ep, True):
-        # stride-2 input gradient by output parity: four problems of 1 + 2 + 2 + 4 taps over a quarter of the pixels each = 1/4 of the walk
-        PROFILE_HINT = ('group', _conv_dgrad_s2(dy, B, g, wb, out, ep, describe=True), 0.25)
-    elif PROFILE is not None and dtype == BF16 and _dil_halves_ok(dtype, dy, g, wb, out, ep, True, True):
-        PROFILE_HINT = ('group', _conv_dil_halves(dy, B, g, wb, out, ep, True, False, describe=True), 2.0 / 3.0)
-    igemm(dtype, M, g.Ci, g.taps * g.Co, dy, dy.stride(0), wb, g.taps * g.Co, out, out.stride(0), conv=conv,
-          transposed=0 if g.plain else 1, **ep)
-    PROFILE_HINT = None
-    return out
+        out = torch.empty((B * g.Hi * g.Wi, g.Ci), device=dy.device, dtype=TORCH_DTYPE[dtype])
+    return _conv('dgrad', dtype, dy, B, g, wb, out, ep)
 
 
 # The input gradient of a stride-s 1x1 projection (pad 0: the skip path of layer2's / layer3's block 0) is non-zero only on the pixels the

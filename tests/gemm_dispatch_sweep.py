@@ -73,7 +73,7 @@ def _wgrad(L, c, code):
 
 
 def _s2_parity_jobs(L, B, Hi, Wi, Ci, Co, x3, ep):
-    """the four problems of ops._conv_dgrad_s2: the stride-2 3x3 input gradient by output parity (omap + btap, awrap on split operands)"""
+    """the four problems of ops.conv_group_jobs('s2_parity', ...): the stride-2 3x3 input gradient by output parity (omap + btap, awrap on split operands)"""
     Ho, Wo, C3 = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1, (3 * Co if x3 else Co)
     jobs = []
     for ph in (0, 1):
@@ -96,7 +96,7 @@ def _s2_parity_jobs(L, B, Hi, Wi, Ci, Co, x3, ep):
 
 
 def _dil_halves_jobs(L, B, H, d, cin, cout, transposed, x3, ep, tile=(128, 128)):
-    """the two problems of ops._conv_dil_halves: a dilated 3x3 convolution on a map of 2 d columns, split by column half"""
+    """the two problems of ops.conv_group_jobs('dil_halves', ...): a dilated 3x3 convolution on a map of 2 d columns, split by column half"""
     Cg = 3 * cin if x3 else cin
     jobs = []
     for half in (0, 1):

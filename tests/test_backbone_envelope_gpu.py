@@ -387,7 +387,8 @@ def test_conv3x3_c64(env, case):
 
     def run(fn, t, **ep):
         out = torch.empty((B * H * W, C), device='cuda', dtype=torch.bfloat16)
-        assert ops._conv3_c64_ok(ops.BF16, t, g, ep, out), (case.name, sorted(ep))
+        kind, w_ = ('fwd', wf) if fn is ops.conv_fwd else ('dgrad', wb)
+        assert ops.conv_form(kind, ops.BF16, t, g, w_, out, ep)[0] == 'direct3x3', (case.name, sorted(ep))
         poison()
         out.fill_(float('nan'))
         with L.launch_log() as log:

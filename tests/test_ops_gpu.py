@@ -755,7 +755,7 @@ def test_one_bit_relu_masks_in_the_gemm_epilogue(ops, dt, M, N, K):
 @pytest.mark.parametrize('B,Hi,Wi,C', [(2, 63, 8, 256), (3, 125, 16, 128), (2, 64, 8, 256), (1, 7, 5, 64), (64, 63, 8, 256), (2, 1, 16, 128)])
 @pytest.mark.parametrize('epilogue', ['plain', 'mask_bits+res'])
 def test_stride2_dgrad_by_output_parity_equals_the_transposed_gather(ops, B, Hi, Wi, C, epilogue):
-    """the input gradient of a stride-2 3x3 convolution as four regular sub-convolutions by output parity (ops._conv_dgrad_s2: one grouped
+    """the input gradient of a stride-2 3x3 convolution as four regular sub-convolutions by output parity (ops.conv_form's 's2_parity': one grouped
     launch, tap blocks of the packed weight read in place, outputs interleaved through SedtIgemm.omap) against (a) the plain transposed
     gather it replaces and (b) torch's conv_transpose2d in f32 on the bf16-rounded operands; odd and even heights / widths, a single row,
     the residual operand and the 1-bit ReLU mask indexed by the dx pixel"""
@@ -798,7 +798,7 @@ def test_stride2_dgrad_by_output_parity_equals_the_transposed_gather(ops, B, Hi,
 @pytest.mark.parametrize('H', [32, 31])
 def test_dilated_conv_by_column_halves_equals_the_plain_gather(ops, H):
     """layer4's dilated 3x3 (dilation 2, padding 2, four columns) as two column halves of six taps each in one grouped ping-pong launch
-    (ops._conv_dil_halves) against the nine-tap gather it replaces and against torch in f32 on the bf16-rounded operands: forward with
+    (ops.conv_form's 'dil_halves') against the nine-tap gather it replaces and against torch in f32 on the bf16-rounded operands: forward with
     FrozenBN + ReLU, input gradient with the 1-bit ReLU mask; URBAN-SED (32 rows) and DCASE (31 rows) maps at C2's batch"""
     import torch.nn.functional as F
     from sound_event_detection_transformer_amd import lib as L

@@ -109,7 +109,7 @@ def test_x3_fast_path_on_the_lds_dma_kernels_against_f64():
             w2 = (torch.randn(256, 256, 3, 3, generator=g) / (9 * 256) ** 0.5).cuda()
             _, w2b = ops.pack_conv(L.F32, w2)
             dy = torch.randn(B * g2.Ho * g2.Wo, 256, generator=g).cuda()
-            # (by output parity - ops._conv_dgrad_s2 - with a residual and an f32 ReLU mask indexed by the dx pixel)
+            # (by output parity - ops.conv_form's 's2_parity' - with a residual and an f32 ReLU mask indexed by the dx pixel)
             res2 = torch.randn(B * 63 * 8, 256, generator=g).cuda()
             mk2 = torch.randn(B * 63 * 8, 256, generator=g).cuda()
             dx = ops.conv_dgrad(L.F32, dy, B, g2, w2b, res=res2, ldr=256, mask=mk2, ldm=256)
@@ -143,7 +143,7 @@ def test_x3_fast_path_on_the_lds_dma_kernels_against_f64():
 
 def test_x3_dilated_conv_by_column_halves_against_f64():
     """layer4's dilated 3x3 at C2's batch in the fast bf16x3 mode: forward and input gradient as two six-tap column halves each
-    (ops._conv_dil_halves with operand images, SedtIgemm.awrap / btap / omap / f32ep together) against f64"""
+    (ops.conv_form's 'dil_halves' with operand images, SedtIgemm.awrap / btap / omap / f32ep together) against f64"""
     import torch.nn.functional as F
     from sound_event_detection_transformer_amd import ops, lib as L
     g = torch.Generator().manual_seed(12)
