@@ -41,6 +41,8 @@
  *                                                                             utilities/metrics.py:120-145, 325-330 (psds_eval)
  *   sedt_stitch_events                                                        no counterpart (the reference scores 10 s clips only):
  *                                                                             the windows' event records -> one list per recording
+ *   sedt_stitch_stream / sedt_stream_reset / sedt_stream_append / sedt_stream_cut   no counterpart: live streams - waveform rings on
+ *                                                                             the device, the same sweep one window per launch
  *   sedt_recording_event_counts / sedt_recording_segment_counts               no counterpart: those lists against a recording's annotations,
  *                                                                             sed_eval's event- and segment-based counts at every threshold
  *   sedt_recording_psds_counts                                                no counterpart: PSDS confusion counts from those lists
@@ -919,6 +921,52 @@ int sedt_psds_update(const int32_t* records, const int32_t* clip_idx, const int3
 int sedt_stitch_events(const int32_t* records, const int32_t* win_off, const double* win_start, const double* rec_dur, int K, int W,
                        int W_stride, int R, int Q, int C, double merge_gap, int cap, int32_t* count, int32_t* out, int32_t* status,
                        void* stream);
+
+/* sedt_stitch_stream (no counterpart in the reference; DESIGN.md section 4, "Live streams", holds the definition and
+ * tests/stream_ref.py restates it): the sweep of sedt_stitch_events ONE window per launch for S live streams, the open set of every
+ * (threshold, stream) kept in `state` between launches.  Grid (S, K), one wave each; both kernels are built from the same window step
+ * (csrc/stitch_sweep.h).  Per stream s:
+ *   action[s]     0 skip (the wave returns at once); 1 add this window; 2 flush: everything open is final; 3 add this window, then flush
+ *   row[s]        the row of records [K][B][1 + 5 Q] that holds the stream's window
+ *   t_w[s], dur[s]  float64: the window's start and the duration its events are clipped against - the win_start[w] and rec_dur[r] of
+ *                 sedt_stitch_events
+ *   win_index[s]  the window's index inside the stream: the `window` word of its events
+ * state: sedt_stitch_stream_state_bytes(K, S) bytes, 8-byte aligned, [K][S] blocks of a header {N, status, windows_seen, pad, last t_w
+ *   f64, count[c] from word 6: events of class c emitted so far} of 72 words and the 640 open entries' fields array by array (onset,
+ *   offset, provider's onset f64; score f32; n_merged, window, query, slot, class int32).  All zeros is a fresh stream
+ *   (sedt_stream_reset, or a memset of the whole state before first use).  Only N entries are read and written; the working set in LDS
+ *   and the overflow condition N + kept candidates > 640 are those of sedt_stitch_events.
+ * Emission: the final events of a launch are appended to emit [K][S][emit_cap][10 words] {onset f64, offset f64, score f32, n_merged,
+ *   window, query, class, pad = 0} at emit_count [K][S] (in/out; it keeps counting past emit_cap and slots at or past the cap are not
+ *   touched).  The events a window's step makes final are ordered by (class, onset); with action 3 those of the flush follow those of
+ *   the window's own step, again by (class, onset) - within a class the whole launch is in onset order.
+ * Defining property: windows w = 0 .. n-1 of a stream fed one per launch with action 1 and a final 2 (or the last with 3) emit, grouped
+ *   by class, the count, the six event words, the per-class order and the status sedt_stitch_events gives for the same records with
+ *   win_start = t_w and rec_dur = dur.
+ * status [K][S] int32, written for every stream whose action is not 0; a raised status is kept in the state and is sticky: from then
+ *   on the stream emits nothing (emit_count does not move, the state does not change) and the status is reported again.
+ *   1 t_w below the stream's previous t_w, or NaN; 2 working set overflow; 4 a kept candidate has on < t_w; 8 row outside 0 .. B-1.
+ * Plain stores and integer LDS adds only, no floating-point atomics, fp contraction off: two identical sequences of launches give
+ * identical bytes.  1 <= Q <= 64, 1 <= C <= 63, 1 <= K <= 1024, 1 <= S <= 65535, B >= 1, merge_gap finite and >= 0, emit_cap >= 1.
+ * sedt_stream_reset: the headers and status words of the streams with which[s] != 0 (which == NULL: all) read zero afterwards. */
+int64_t sedt_stitch_stream_state_bytes(int K, int S);
+int sedt_stitch_stream(const int32_t* records, const int32_t* action, const int32_t* row, const double* t_w, const double* dur,
+                       const int32_t* win_index, int K, int S, int B, int Q, int C, double merge_gap, int emit_cap, int32_t* state,
+                       int64_t state_bytes, int32_t* emit, int32_t* emit_count, int32_t* status, void* stream);
+int sedt_stream_reset(int32_t* state, int64_t state_bytes, const int32_t* which, int K, int S, int32_t* status, void* stream);
+
+/* sedt_stream_append / sedt_stream_cut (csrc/stream.hip; no counterpart in the reference): the waveform rings of S live streams, one
+ * [S][ring_samples] float32 device tensor.  Jobs are int32 tables of four words a job, given twice: `jobs_host` is checked here,
+ * `jobs` is the device copy the kernel reads (it skips a job that is out of range).  Dword loads and stores only.
+ *   append  job {stream, ring write position, offset into the flat staged vector src [src_len], n}: n samples into the stream's ring,
+ *           wrapping at ring_samples (n <= ring_samples).  One launch for all jobs; n_jobs == 0 launches nothing.
+ *   cut     job {stream, ring read position, length, destination row}: wave[row][0 .. length) from the ring across the wrap point,
+ *           wave[row][length .. window) zeros; a row of wave [B][window] without a job is zeroed whole.  One launch fills all B rows.
+ * Positions inside 0 .. ring_samples-1, length <= window <= ring_samples, streams and rows in range, one job per row at the most. */
+int sedt_stream_append(const float* src, int64_t src_len, const int32_t* jobs_host, const int32_t* jobs, int n_jobs, float* ring, int S,
+                       int ring_samples, void* stream);
+int sedt_stream_cut(const float* ring, int S, int ring_samples, const int32_t* jobs_host, const int32_t* jobs, int n_jobs, float* wave, int B,
+                    int window, void* stream);
 
 /* sedt_recording_event_counts / sedt_recording_segment_counts (no counterpart in the reference, which scores 10 s dataset clips only;
  * DESIGN.md section 4, "Scoring recordings", holds the definition and tests/recording_metrics_ref.py restates it): the stitched event

@@ -1,37 +1,26 @@
 // stitch.hip - recordings of any length: the event records of a recording's overlapping windows (decode_events_kernel, decode.hip)
 // merged into one event list per (threshold, recording, class)
 //   * stitch_events_kernel   an event a window boundary cut in two, or one that two overlapping windows both report, becomes one event
-// The reference scores 10 s dataset clips only and has no counterpart; DESIGN.md section 4 ("Recordings of any length") holds the
-// definition and tests/recording_ref.py restates it in NumPy.
+//   * stitch_stream_kernel   the same sweep one window per launch for S live streams, the open set kept in global memory between launches
+//   * stream_reset_kernel    chosen streams start again at time 0
+// The reference scores 10 s dataset clips only and has no counterpart; DESIGN.md section 4 ("Recordings of any length", "Live
+// streams") holds the definition and tests/recording_ref.py / tests/stream_ref.py restate it in NumPy.
 // One wave per (recording, threshold) sweeps the recording's windows in start order with the OPEN merged events in LDS.  An event of
 // window w cannot start before t_w, so a merged event with off + merge_gap < t_w can gain no member once window w is reached: it is
 // written out and leaves the set.  What stays open at window w comes from the few earlier windows that still reach t_w (D of them,
 // D <= 8 by the Python side's plan check), at most D * Q events of all classes together - a recording of any number of windows runs
 // in the same 36 KB of LDS.  Float64 adds and compares on the records' f32 values widened; plain stores, integer LDS operations only:
 // the result does not depend on launch order and two launches give the same bytes.
+// The body of the window loop is stitch_sweep_step (stitch_sweep.h); both kernels are built from it.
 #include <cmath>
 
 #include "common.h"
 #include "event_records.h"
+#include "stitch_sweep.h"
 
 #pragma clang fp contract(off)     // t_w + on32, off + merge_gap: the plain float64 add and compare of the definition
 
 namespace sedt {
-
-#define SEDT_ST_OPEN 640           // open merged events + the candidates of the window being added: (8 + 1) * 64 and a chunk to spare
-
-#define SEDT_ST_UNORDERED 1        // status bits: win_start of the recording not ascending (or NaN)
-#define SEDT_ST_OVERFLOW 2         //   more than SEDT_ST_OPEN open events + candidates at some window
-#define SEDT_ST_EARLY 4            //   a kept candidate starts before its window does (a negative onset in a record)
-#define SEDT_ST_TABLE 8            //   win_off[r] .. win_off[r + 1] is not a range inside 0 .. W
-
-// the member of a merged event that gives score, window and query: the highest score; among equal scores the first in (on, w, s)
-__device__ __forceinline__ bool st_better(float sa, double oa, int wa, int la, float sb, double ob, int wb, int lb) {
-  if (sa != sb) return sa > sb;
-  if (oa != ob) return oa < ob;
-  if (wa != wb) return wa < wb;
-  return la < lb;
-}
 
 // block = 64 threads = one wave, blockIdx.x = recording, blockIdx.y = threshold.
 __global__ __launch_bounds__(64) void stitch_events_kernel(const int32_t* __restrict__ records, const int32_t* __restrict__ win_off,
@@ -39,21 +28,12 @@ __global__ __launch_bounds__(64) void stitch_events_kernel(const int32_t* __rest
                                                            int W, int W_stride, int R, int Q, int C, double gap, int cap,
                                                            int32_t* __restrict__ count, int32_t* __restrict__ out,
                                                            int32_t* __restrict__ status) {
-  // the open merged events (all classes, unordered; class -1 = absorbed into another entry, dropped at the next compaction)
-  __shared__ double o_on[SEDT_ST_OPEN], o_off[SEDT_ST_OPEN], o_pon[SEDT_ST_OPEN];       // onset, offset, onset of the providing member
-  __shared__ float o_score[SEDT_ST_OPEN];
-  __shared__ int o_n[SEDT_ST_OPEN], o_win[SEDT_ST_OPEN], o_q[SEDT_ST_OPEN], o_slot[SEDT_ST_OPEN], o_cls[SEDT_ST_OPEN], o_fin[SEDT_ST_OPEN];
-  // the kept candidates of the window being added, in slot order
-  __shared__ double c_on[SEDT_MAX_QUERIES], c_off[SEDT_MAX_QUERIES];
-  __shared__ float c_score[SEDT_MAX_QUERIES];
-  __shared__ int c_cls[SEDT_MAX_QUERIES], c_q[SEDT_MAX_QUERIES], c_slot[SEDT_MAX_QUERIES];
-  __shared__ int s_cnt[SEDT_MAX_CLASSES + 1];
+  __shared__ StitchSet S;
 
   const int r = blockIdx.x, kt = blockIdx.y, lane = threadIdx.x;
-  const unsigned long long lt = (1ull << lane) - 1ull;
   int32_t* cnt_out = count + ((long)kt * R + r) * C;
   int32_t* out_r = out + ((long)kt * R + r) * C * (long)cap * SEDT_EVENT_WORDS;
-  if (lane <= SEDT_MAX_CLASSES) s_cnt[lane] = 0;
+  if (lane <= SEDT_MAX_CLASSES) S.s_cnt[lane] = 0;
   const int w0 = win_off[r], w1 = win_off[r + 1];
   int st = 0;
   if (w0 < 0 || w1 < w0 || w1 > W) st = SEDT_ST_TABLE;
@@ -69,126 +49,145 @@ __global__ __launch_bounds__(64) void stitch_events_kernel(const int32_t* __rest
   int N = 0;                                                            // entries of the open set (wave-uniform)
   __syncthreads();
 
+  // a final event is written at count[class] + its rank by onset among the final ones of the class
+  auto emit = [&](int i, int cls, double on, int rank) {
+    const long pos = (long)S.s_cnt[cls] + rank;
+    if (pos < cap) {
+      int32_t* e = out_r + ((long)cls * cap + pos) * SEDT_EVENT_WORDS;
+      reinterpret_cast<double*>(e)[0] = on;
+      reinterpret_cast<double*>(e)[1] = S.o_off[i];
+      e[SEDT_EVENT_SCORE] = __float_as_int(S.o_score[i]);
+      e[SEDT_EVENT_MERGED] = S.o_n[i];
+      e[SEDT_EVENT_WINDOW] = S.o_win[i];
+      e[SEDT_EVENT_QUERY] = S.o_q[i];
+    }
+  };
   for (int w = w0; w <= w1 && !st; ++w) {
     const bool flush = w == w1;                                         // after the last window: everything still open is final
-    const double tw = flush ? 0.0 : win_start[w];
-
-    // ---- the window's kept candidates (one lane per slot)
-    int n_kept = 0;
-    if (!flush) {
-      const int32_t* rec = record_at(records, kt, W_stride, w, Q);
-      const int n_w = rec[0];
-      bool kept = false;
-      double on = 0.0, off = 0.0;
-      float sc = 0.f;
-      int cls = -1, q = -1;
-      if (n_w >= 0 && n_w <= Q && lane < n_w) {                         // a count outside 0 .. Q: the record is skipped whole
-        const int32_t* s = record_slot(rec, lane);
-        cls = s[SEDT_REC_CLASS];
-        const double a = tw + (double)__int_as_float(s[SEDT_REC_ONSET]), b = tw + (double)__int_as_float(s[SEDT_REC_OFFSET]);
-        on = a > dur ? dur : a;                                         // min(., rec_dur); a NaN stays one and fails the compare below
-        off = b > dur ? dur : b;
-        sc = __int_as_float(s[SEDT_REC_SCORE]);
-        q = s[SEDT_REC_QUERY];
-        kept = cls >= 0 && cls < C && (off - on) > 0.0 && sc == sc;
-      }
-      if (__ballot(kept && on < tw)) { st = SEDT_ST_EARLY; break; }
-      const unsigned long long km = __ballot(kept);
-      n_kept = __popcll(km);
-      if (kept) {
-        const int p = __popcll(km & lt);
-        c_on[p] = on; c_off[p] = off; c_score[p] = sc; c_cls[p] = cls; c_q[p] = q; c_slot[p] = lane;
-      }
-    }
-
-    // ---- final events: off + merge_gap < t_w.  Written at count[class] + their rank by onset among the final ones of the class
-    // (merged events of one class are disjoint, so their onsets differ), then taken out of the set
-    for (int i = lane; i < N; i += 64) o_fin[i] = o_cls[i] >= 0 && (flush || o_off[i] + gap < tw);
-    __syncthreads();
-    for (int i = lane; i < N; i += 64) {
-      if (!o_fin[i]) continue;
-      const int cls = o_cls[i];
-      const double on = o_on[i];
-      int rank = 0;
-      for (int j = 0; j < N; ++j) rank += (o_fin[j] && o_cls[j] == cls && o_on[j] < on) ? 1 : 0;
-      const long pos = (long)s_cnt[cls] + rank;
-      if (pos < cap) {
-        int32_t* e = out_r + ((long)cls * cap + pos) * SEDT_EVENT_WORDS;
-        reinterpret_cast<double*>(e)[0] = on;
-        reinterpret_cast<double*>(e)[1] = o_off[i];
-        e[SEDT_EVENT_SCORE] = __float_as_int(o_score[i]);
-        e[SEDT_EVENT_MERGED] = o_n[i];
-        e[SEDT_EVENT_WINDOW] = o_win[i];
-        e[SEDT_EVENT_QUERY] = o_q[i];
-      }
-    }
-    __syncthreads();
-    for (int i = lane; i < N; i += 64)
-      if (o_fin[i]) atomicAdd(&s_cnt[o_cls[i]], 1);                      // integer LDS add: the sum does not depend on the order
-    __syncthreads();
-    int M = 0;                                                          // compaction, in place: chunk by chunk, order kept
-    for (int base = 0; base < N; base += 64) {
-      const int i = base + lane;
-      const bool stay = i < N && o_cls[i] >= 0 && !o_fin[i];
-      double a = 0.0, b = 0.0, c = 0.0;
-      float sc = 0.f;
-      int n = 0, wi = 0, q = 0, sl = 0, cl = 0;
-      if (stay) { a = o_on[i]; b = o_off[i]; c = o_pon[i]; sc = o_score[i]; n = o_n[i]; wi = o_win[i]; q = o_q[i]; sl = o_slot[i]; cl = o_cls[i]; }
-      const unsigned long long sm = __ballot(stay);
-      __syncthreads();
-      if (stay) {
-        const int d = M + __popcll(sm & lt);                            // d <= i: an entry moves towards the front, inside chunks already read
-        o_on[d] = a; o_off[d] = b; o_pon[d] = c; o_score[d] = sc; o_n[d] = n; o_win[d] = wi; o_q[d] = q; o_slot[d] = sl; o_cls[d] = cl;
-      }
-      M += __popcll(sm);
-      __syncthreads();
-    }
-    N = M;
-    if (flush) break;
-    if (N + n_kept > SEDT_ST_OPEN) { st = SEDT_ST_OVERFLOW; break; }
-
-    // ---- the candidates join the set one after the other.  A candidate and an open event of its class belong together when each
-    // starts no later than the other's offset + merge_gap; the open events of a class are disjoint components, so the candidate and
-    // everything it touches become one entry (the first touched, else a new one) and the others are marked absorbed.  Every value
-    // below is wave-uniform but `hit`; lane 0 writes.
-    const int wr = w - w0;
-    for (int c = 0; c < n_kept; ++c) {
-      const int cc = c_cls[c];
-      double on = c_on[c], off = c_off[c], pon = on;
-      float sc = c_score[c];
-      int n = 1, wi = wr, q = c_q[c], sl = c_slot[c], first = -1;
-      const double reach = off + gap, start = on;                       // the candidate's own: the merged entry grows, its test does not
-      for (int base = 0; base < N; base += 64) {
-        const int i = base + lane;
-        const bool hit = i < N && o_cls[i] == cc && start <= o_off[i] + gap && o_on[i] <= reach;
-        unsigned long long hm = __ballot(hit);
-        while (hm) {
-          const int j = base + (int)__ffsll((long long)hm) - 1;
-          hm &= hm - 1ull;
-          const double jo = o_on[j], je = o_off[j], jp = o_pon[j];
-          const float js = o_score[j];
-          const int jw = o_win[j], jl = o_slot[j];
-          on = jo < on ? jo : on;
-          off = je > off ? je : off;
-          n += o_n[j];
-          if (st_better(js, jp, jw, jl, sc, pon, wi, sl)) { sc = js; pon = jp; wi = jw; sl = jl; q = o_q[j]; }
-          if (first < 0) first = j;
-          else if (lane == 0) o_cls[j] = -1;
-        }
-      }
-      const int d = first >= 0 ? first : N;
-      if (lane == 0) {
-        o_on[d] = on; o_off[d] = off; o_pon[d] = pon; o_score[d] = sc; o_n[d] = n; o_win[d] = wi; o_q[d] = q; o_slot[d] = sl; o_cls[d] = cc;
-      }
-      if (first < 0) ++N;
-      __syncthreads();
-    }
+    st = stitch_sweep_step<false>(S, N, flush, flush ? records : record_at(records, kt, W_stride, w, Q), flush ? 0.0 : win_start[w], dur,
+                                  w - w0, Q, C, gap, lane, emit);
   }
 
   // ---- counts and status.  With a status raised the lists are not to be used: their counts read 0
   __syncthreads();
-  if (lane < C) cnt_out[lane] = st ? 0 : s_cnt[lane];
+  if (lane < C) cnt_out[lane] = st ? 0 : S.s_cnt[lane];
   if (lane == 0) status[(long)kt * R + r] = st;
+}
+
+// ---- live streams.  The state of one (threshold, stream), SEDT_SS_WORDS 32-bit words in global memory, 8-byte aligned:
+//   header  {N, status, windows_seen, pad, last t_w (f64, words 4-5), count[c] at word SEDT_SS_COUNT + c: the events of class c emitted so far}
+//   fields  of the SEDT_ST_OPEN entries of the open set, array by array in StitchSet's order (o_fin is scratch and not kept)
+// All zeros is a fresh stream.  Only the first N entries of every array are read and written.
+#define SEDT_SS_COUNT 6
+#define SEDT_SS_HDR 72
+#define SEDT_SS_WORDS (SEDT_SS_HDR + 12 * SEDT_ST_OPEN)
+#define SEDT_EMIT_WORDS 10         // {onset f64, offset f64, score f32, n_merged, window, query, class, pad}
+enum { SEDT_EMIT_CLASS = 8, SEDT_EMIT_PAD };
+
+__device__ __forceinline__ int wave_sum(int v) {
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// block = 64 threads = one wave, blockIdx.x = stream, blockIdx.y = threshold.
+__global__ __launch_bounds__(64) void stitch_stream_kernel(const int32_t* __restrict__ records, const int32_t* __restrict__ action,
+                                                           const int32_t* __restrict__ row, const double* __restrict__ t_w,
+                                                           const double* __restrict__ dur, const int32_t* __restrict__ win_index,
+                                                           int NS, int B, int Q, int C, double gap, int emit_cap,
+                                                           int32_t* __restrict__ state, int32_t* __restrict__ emit,
+                                                           int32_t* __restrict__ emit_count, int32_t* __restrict__ status) {
+  __shared__ StitchSet S;
+
+  const int s = blockIdx.x, kt = blockIdx.y, lane = threadIdx.x;
+  const int act = action[s];
+  if (act < 1 || act > 3) return;                                       // 0: this stream has no window in this launch
+  const long ks = (long)kt * NS + s;
+  int32_t* hdr = state + ks * SEDT_SS_WORDS;
+  int st = hdr[1];
+  if (st) {                                                             // sticky: the stream emits nothing more, its status is reported
+    if (lane == 0) status[ks] = st;
+    return;
+  }
+  int N = hdr[0];
+  N = N < 0 ? 0 : (N > SEDT_ST_OPEN ? SEDT_ST_OPEN : N);
+  const int seen = hdr[2];
+  const double last = reinterpret_cast<const double*>(hdr)[2];
+  double* g_on = reinterpret_cast<double*>(hdr + SEDT_SS_HDR);
+  double* g_off = g_on + SEDT_ST_OPEN;
+  double* g_pon = g_off + SEDT_ST_OPEN;
+  int32_t* g_score = reinterpret_cast<int32_t*>(g_pon + SEDT_ST_OPEN);
+  int32_t *g_n = g_score + SEDT_ST_OPEN, *g_win = g_n + SEDT_ST_OPEN, *g_q = g_win + SEDT_ST_OPEN, *g_slot = g_q + SEDT_ST_OPEN,
+          *g_cls = g_slot + SEDT_ST_OPEN;
+  if (lane <= SEDT_MAX_CLASSES) S.s_cnt[lane] = lane < C ? hdr[SEDT_SS_COUNT + lane] : 0;
+  for (int i = lane; i < N; i += 64) {
+    S.o_on[i] = g_on[i]; S.o_off[i] = g_off[i]; S.o_pon[i] = g_pon[i]; S.o_score[i] = __int_as_float(g_score[i]); S.o_n[i] = g_n[i];
+    S.o_win[i] = g_win[i]; S.o_q[i] = g_q[i]; S.o_slot[i] = g_slot[i]; S.o_cls[i] = g_cls[i];
+  }
+  __syncthreads();
+  const int cnt0 = lane < C ? S.s_cnt[lane] : 0;
+  const int e0 = emit_count[ks];
+  int32_t* emit_s = emit + ks * (long)emit_cap * SEDT_EMIT_WORDS;
+  int base = e0;                                                        // where this step's final events go: rank by (class, onset) behind it
+
+  auto out = [&](int i, int cls, double on, int rank) {
+    const long pos = (long)base + rank;
+    if (pos >= 0 && pos < emit_cap) {
+      int32_t* e = emit_s + pos * SEDT_EMIT_WORDS;
+      reinterpret_cast<double*>(e)[0] = on;
+      reinterpret_cast<double*>(e)[1] = S.o_off[i];
+      e[SEDT_EVENT_SCORE] = __float_as_int(S.o_score[i]);
+      e[SEDT_EVENT_MERGED] = S.o_n[i];
+      e[SEDT_EVENT_WINDOW] = S.o_win[i];
+      e[SEDT_EVENT_QUERY] = S.o_q[i];
+      e[SEDT_EMIT_CLASS] = cls;
+      e[SEDT_EMIT_PAD] = 0;
+    }
+  };
+  const double tw = (act & 1) ? t_w[s] : 0.0;
+  if (act & 1) {
+    const int r = row[s];
+    if (r < 0 || r >= B) st = SEDT_ST_TABLE;
+    else if (!(tw == tw) || (seen > 0 && !(tw >= last))) st = SEDT_ST_UNORDERED;
+    else st = stitch_sweep_step<true>(S, N, false, record_at(records, kt, B, r, Q), tw, dur[s], win_index[s], Q, C, gap, lane, out);
+  }
+  if (!st && (act & 2)) {
+    __syncthreads();
+    base = e0 + wave_sum(lane < C ? S.s_cnt[lane] - cnt0 : 0);          // behind what the window's own step wrote (action 3)
+    stitch_sweep_step<true>(S, N, true, records, 0.0, 0.0, 0, Q, C, gap, lane, out);
+  }
+
+  __syncthreads();
+  if (st) {                                                             // raised now: the state stays as it was but for the status word,
+    if (lane == 0) { hdr[1] = st; status[ks] = st; }                    // emit_count does not move (slots behind it may have been written)
+    return;
+  }
+  const int total = wave_sum(lane < C ? S.s_cnt[lane] - cnt0 : 0);
+  if (lane < C) hdr[SEDT_SS_COUNT + lane] = S.s_cnt[lane];
+  for (int i = lane; i < N; i += 64) {
+    g_on[i] = S.o_on[i]; g_off[i] = S.o_off[i]; g_pon[i] = S.o_pon[i]; g_score[i] = __float_as_int(S.o_score[i]); g_n[i] = S.o_n[i];
+    g_win[i] = S.o_win[i]; g_q[i] = S.o_q[i]; g_slot[i] = S.o_slot[i]; g_cls[i] = S.o_cls[i];
+  }
+  if (lane == 0) {
+    hdr[0] = N;
+    if (act & 1) {
+      hdr[2] = seen + 1;
+      reinterpret_cast<double*>(hdr)[2] = tw;
+    }
+    emit_count[ks] = e0 + total;
+    status[ks] = 0;
+  }
+}
+
+// one thread per header word of (threshold, stream): the chosen streams' headers and status words read zero afterwards
+__global__ void stream_reset_kernel(int32_t* __restrict__ state, const int32_t* __restrict__ which, long n, int NS,
+                                    int32_t* __restrict__ status) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long ks = i / SEDT_SS_HDR;
+  const int word = (int)(i - ks * SEDT_SS_HDR);
+  if (which && !which[ks % NS]) return;
+  state[ks * SEDT_SS_WORDS + word] = 0;
+  if (word == 0) status[ks] = 0;
 }
 
 }  // namespace sedt
@@ -211,4 +210,43 @@ extern "C" int sedt_stitch_events(const int32_t* records, const int32_t* win_off
   hipLaunchKernelGGL(stitch_events_kernel, dim3(R, K), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), records, win_off, win_start,
                      rec_dur, W, W_stride, R, Q, C, merge_gap, cap, count, out, status);
   return check_launch("stitch_events");
+}
+
+extern "C" int64_t sedt_stitch_stream_state_bytes(int K, int S) {
+  return (int64_t)(K > 0 ? K : 0) * (S > 0 ? S : 0) * SEDT_SS_WORDS * 4;
+}
+
+extern "C" int sedt_stitch_stream(const int32_t* records, const int32_t* action, const int32_t* row, const double* t_w, const double* dur,
+                                  const int32_t* win_index, int K, int S, int B, int Q, int C, double merge_gap, int emit_cap,
+                                  int32_t* state, int64_t state_bytes, int32_t* emit, int32_t* emit_count, int32_t* status, void* stream) {
+  using namespace sedt;
+  SEDT_REQUIRE(Q >= 1 && Q <= SEDT_MAX_QUERIES && C >= 1 && C <= SEDT_MAX_CLASSES, "stitch_stream: Q=%d (1 .. %d) C=%d (1 .. %d)", Q, SEDT_MAX_QUERIES,
+               C, SEDT_MAX_CLASSES);
+  SEDT_REQUIRE(K >= 1 && K <= SEDT_MAX_THRESHOLDS, "stitch_stream: %d thresholds (1 .. %d)", K, SEDT_MAX_THRESHOLDS);
+  SEDT_REQUIRE(S >= 1 && S <= 65535 && B >= 1, "stitch_stream: S=%d (1 .. 65535) B=%d (>= 1)", S, B);
+  SEDT_REQUIRE(merge_gap >= 0.0 && merge_gap < INFINITY, "stitch_stream: merge_gap %.17g is not a finite number >= 0", merge_gap);
+  SEDT_REQUIRE(emit_cap >= 1, "stitch_stream: emit_cap=%d (>= 1)", emit_cap);
+  SEDT_REQUIRE((double)K * S * emit_cap * SEDT_EMIT_WORDS * 4.0 <= 4294967296.0, "stitch_stream: an emit buffer of K=%d x S=%d x emit_cap=%d "
+               "events is larger than 4 GiB", K, S, emit_cap);
+  SEDT_REQUIRE(records && action && row && t_w && dur && win_index && state && emit && emit_count && status, "stitch_stream: null pointer");
+  SEDT_REQUIRE(state_bytes >= sedt_stitch_stream_state_bytes(K, S), "stitch_stream: a state of %lld bytes, K=%d x S=%d streams take %lld",
+               (long long)state_bytes, K, S, (long long)sedt_stitch_stream_state_bytes(K, S));
+  SEDT_REQUIRE((reinterpret_cast<uintptr_t>(emit) & 7) == 0 && (reinterpret_cast<uintptr_t>(state) & 7) == 0,
+               "stitch_stream: emit and state are not 8-byte aligned");
+  hipLaunchKernelGGL(stitch_stream_kernel, dim3(S, K), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), records, action, row, t_w, dur,
+                     win_index, S, B, Q, C, merge_gap, emit_cap, state, emit, emit_count, status);
+  return check_launch("stitch_stream");
+}
+
+extern "C" int sedt_stream_reset(int32_t* state, int64_t state_bytes, const int32_t* which, int K, int S, int32_t* status, void* stream) {
+  using namespace sedt;
+  SEDT_REQUIRE(K >= 1 && K <= SEDT_MAX_THRESHOLDS && S >= 1 && S <= 65535, "stream_reset: K=%d (1 .. %d) S=%d (1 .. 65535)", K,
+               SEDT_MAX_THRESHOLDS, S);
+  SEDT_REQUIRE(state && status, "stream_reset: null pointer");
+  SEDT_REQUIRE(state_bytes >= sedt_stitch_stream_state_bytes(K, S), "stream_reset: a state of %lld bytes, K=%d x S=%d streams take %lld",
+               (long long)state_bytes, K, S, (long long)sedt_stitch_stream_state_bytes(K, S));
+  const long n = (long)K * S * SEDT_SS_HDR;
+  hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), state,
+                     which, n, S, status);
+  return check_launch("stream_reset");
 }

@@ -971,6 +971,24 @@ def detect_recordings(model, postprocessor, decoder, mel, transform, waves, file
     return det(waves, filenames, sample_rates)
 
 
+def detect_stream(detector, chunk_iter):
+    """live streams through a utilities.stream.StreamDetector: a generator.  ``chunk_iter`` yields one list of chunks per push (one
+    1-D chunk per stream of the detector, any lengths), or (chunks, streams) to name the streams; every push yields its
+    {at_m: StreamEvents} - the events that became final with it - and when the iterator ends, the streams are finished and the
+    closing events are yielded.  The next push is submitted before the previous one's result is formatted."""
+    pending = None
+    for item in chunk_iter:
+        chunks, streams = item if isinstance(item, tuple) else (item, None)
+        nxt = detector.push(chunks, streams)
+        if pending is not None:
+            yield pending.result()
+        pending = nxt
+    last = detector.finish()
+    if pending is not None:
+        yield pending.result()
+    yield last.result()
+
+
 def evaluate_recordings(detector, metrics, calls):
     """annotated recordings of any length scored without leaving the device: ``detector`` a utilities.recording.RecordingDetector,
     ``metrics`` a utilities.recording_metrics.RecordingMetrics bound to the detector's decoder, its reference set, ``calls`` an

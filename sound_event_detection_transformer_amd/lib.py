@@ -234,6 +234,11 @@ SIGNATURES = {
     'sedt_event_sweep_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),
     'sedt_psds_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp]),
     'sedt_stitch_events': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    'sedt_stitch_stream_state_bytes': (_i64, [_i, _i]),
+    'sedt_stitch_stream': (_i, [_vp] * 6 + [_i] * 5 + [_d, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'sedt_stream_reset': (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+    'sedt_stream_append': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    'sedt_stream_cut': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'sedt_recording_event_counts': (_i, [_vp] * 7 + [_i] * 8 + [_d, _d, _i, _vp, _vp, _vp, _vp]),
     'sedt_recording_segment_counts': (_i, [_vp] * 8 + [_i] * 8 + [_d, _vp, _vp, _vp, _vp]),
     'sedt_recording_psds_counts': (_i, [_vp] * 9 + [_i] * 8 + [_d, _d, _d, _vp, _vp, _vp, _vp]),

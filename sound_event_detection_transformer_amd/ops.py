@@ -1996,6 +1996,92 @@ def stitch_events(records, win_off, win_start, rec_dur, n_classes, merge_gap=0.0
     return count, out, status
 
 
+STREAM_EMIT_WORDS = 10            # words of one emitted event: the stitched event's eight, then {class, pad}
+STREAM_OPEN = 640                 # csrc/stitch_sweep.h: SEDT_ST_OPEN, the most events one launch can make final per (threshold, stream)
+
+
+def stitch_stream_state_bytes(K, S):
+    """the bytes of the open-set state of K thresholds x S streams (include/sedt_hip.h: sedt_stitch_stream_state_bytes)"""
+    return int(L.load().sedt_stitch_stream_state_bytes(int(K), int(S)))
+
+
+def stitch_stream_state(K, S, device):
+    """a fresh state for stitch_stream: (state int32 [K * S * words], status int32 [K, S]), zeroed"""
+    n = stitch_stream_state_bytes(K, S) // 4
+    return torch.zeros(n, dtype=torch.int32, device=device), torch.zeros((int(K), int(S)), dtype=torch.int32, device=device)
+
+
+def stitch_stream_views(emit):
+    """typed views on an emit buffer [K, S, emit_cap, 10] (int32; a device tensor, a host tensor or a numpy array alike):
+    (times [K,S,emit_cap,2] f64 {onset, offset}, score [K,S,emit_cap] f32, n_merged, window, query, class [K,S,emit_cap] int32)"""
+    f32, f64 = (torch.float32, torch.float64) if torch.is_tensor(emit) else (np.float32, np.float64)
+    return emit[..., 0:4].view(f64), emit[..., 4].view(f32), emit[..., 5], emit[..., 6], emit[..., 7], emit[..., 8]
+
+
+def stitch_stream(records, action, row, t_w, dur, win_index, n_classes, merge_gap, state, emit, emit_count, status):
+    """one window of each of S live streams into the streams' open sets (``state``: stitch_stream_state's), the events that became
+    final appended to ``emit`` int32 [K, S, emit_cap, 10] at ``emit_count`` int32 [K, S] (in/out): include/sedt_hip.h:
+    sedt_stitch_stream.  records int32 [K, B, 1 + 5 Q]; action, row, win_index int32 [S], t_w, dur float64 [S] on the device;
+    status int32 [K, S].  Nothing is read back."""
+    _dev_check(records, action, row, t_w, dur, win_index, state, emit, emit_count, status)
+    K, B = records.shape[0], records.shape[1]
+    Q = (records.shape[2] - 1) // 5
+    S = action.numel()
+    assert records.dtype == torch.int32 and records.dim() == 3 and records.shape[2] == 1 + 5 * Q and records.is_contiguous()
+    for t in (action, row, win_index):
+        assert t.dtype == torch.int32 and t.numel() == S and t.is_contiguous()
+    for t in (t_w, dur):
+        assert t.dtype == torch.float64 and t.numel() == S and t.is_contiguous()
+    assert emit.dtype == torch.int32 and emit.dim() == 4 and tuple(emit.shape[:2]) == (K, S) and emit.shape[3] == STREAM_EMIT_WORDS
+    assert emit.is_contiguous() and state.dtype == torch.int32 and state.is_contiguous()
+    assert emit_count.dtype == torch.int32 and tuple(emit_count.shape) == (K, S) and emit_count.is_contiguous()
+    assert status.dtype == torch.int32 and tuple(status.shape) == (K, S) and status.is_contiguous()
+    L.check(L.load().sedt_stitch_stream(_p(records), _p(action), _p(row), _p(t_w), _p(dur), _p(win_index), K, S, B, Q, int(n_classes),
+                                        float(merge_gap), int(emit.shape[2]), _p(state), 4 * state.numel(), _p(emit), _p(emit_count),
+                                        _p(status), L.stream_ptr()), 'stitch_stream')
+    return emit, emit_count, status
+
+
+def stream_reset(state, status, which=None):
+    """the streams with which[s] != 0 (int32 [S] on the device; None: all) start again: their headers in ``state`` and their
+    ``status`` [K, S] words read zero afterwards (sedt_stream_reset)"""
+    _dev_check(state, status, which)
+    K, S = status.shape
+    assert state.dtype == torch.int32 and state.is_contiguous() and status.dtype == torch.int32 and status.is_contiguous()
+    assert which is None or (which.dtype == torch.int32 and which.numel() == S and which.is_contiguous())
+    L.check(L.load().sedt_stream_reset(_p(state), 4 * state.numel(), _p(which), K, S, _p(status), L.stream_ptr()), 'stream_reset')
+
+
+def _ring_jobs(jobs_host, jobs):
+    h = np.ascontiguousarray(jobs_host, dtype=np.int32).reshape(-1, 4)
+    if len(h):
+        _dev_check(jobs)
+        assert jobs.dtype == torch.int32 and jobs.numel() >= h.size and jobs.is_contiguous()
+    return h, h.ctypes.data_as(C.c_void_p) if len(h) else None, _p(jobs) if len(h) else None
+
+
+def stream_append(src, jobs_host, jobs, ring):
+    """samples of the flat staged float32 vector ``src`` into the streams' rings ``ring`` float32 [S, ring_samples]: one launch for
+    all jobs {stream, ring write position, offset in src, n} (``jobs_host`` int32 [J, 4] is checked on the host, ``jobs`` is its
+    device copy): sedt_stream_append"""
+    _dev_check(src, ring)
+    assert src.dtype == torch.float32 and src.is_contiguous() and ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous()
+    h, hp, dp = _ring_jobs(jobs_host, jobs)
+    L.check(L.load().sedt_stream_append(_p(src), src.numel(), hp, dp, len(h), _p(ring), ring.shape[0], ring.shape[1], L.stream_ptr()),
+            'stream_append')
+
+
+def stream_cut(ring, jobs_host, jobs, wave):
+    """windows out of the streams' rings into ``wave`` float32 [B, window]: one launch fills every row - a job {stream, ring read
+    position, length, row} copies across the wrap point and zero-pads, a row without a job is zeroed: sedt_stream_cut"""
+    _dev_check(ring, wave)
+    assert wave.dtype == torch.float32 and wave.dim() == 2 and wave.is_contiguous()
+    assert ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous()
+    h, hp, dp = _ring_jobs(jobs_host, jobs)
+    L.check(L.load().sedt_stream_cut(_p(ring), ring.shape[0], ring.shape[1], hp, dp, len(h), _p(wave), wave.shape[0], wave.shape[1],
+                                     L.stream_ptr()), 'stream_cut')
+
+
 def _recording_args(count, out, stitch_status, cap, rec_idx, table, counters, status):
     """the shape, dtype and contiguity asserts the two recording-metrics launches share; returns (K, R, C, n_fusion, status)"""
     _dev_check(count, out, stitch_status, rec_idx, table['off'], table['on'], table['end'], status, *counters)
