@@ -7,6 +7,8 @@ optimizer updates are always seen); gradients are returned as f32 tensors, so DD
 clip_grad_norm_ and AdamW work unchanged.  Every Function saves only what its backward needs and
 recomputes dropout masks from (seed, element index).
 """
+from collections import namedtuple
+
 import torch
 from torch.autograd import Function
 
@@ -880,6 +882,78 @@ class BlockCfg(object):
         self.cin, self.planes, self.stride, self.dil, self.ds = cin, planes, stride, dil, ds
 
 
+BlockPlan = namedtuple('BlockPlan', 'fwd want_ab want_bits mask_x bwd want_g want_gx wgrads')
+
+
+def block_plan(dt, blk, B, H, W, first, mask_input, contiguous, have_xbits, train, need_x_grad, w_rg, have_frags, relu_bits):
+    """How one Bottleneck of a stage runs, both ways, decided once from plain values (no tensor, no GPU).
+    first: the stage's first block; mask_input: the stage input is a ReLU output (its gradient is masked); contiguous / have_xbits: the
+    block input is contiguous / comes with its sign bits; train: some input of the stage needs a gradient; need_x_grad: the stage input
+    does; w_rg: requires_grad of conv1, conv2, conv3 [, projection]; have_frags: all of them have fragment-major images; relu_bits:
+    ops.RELU_BITS.  Returns BlockPlan:
+      fwd        ops.block_form's launch form, or None = the per-op convolutions
+      want_ab    the forward keeps the two intermediates a, b;  want_bits: it writes the sign bits of its output
+      mask_x     the gradient of the block input is masked by that input's ReLU
+      bwd        'skip' (nothing to compute), 'chain' (bneck0: gy -> gb -> ga in one launch, then two input-gradient GEMMs), 'fused'
+                 (the whole input-gradient chain in one launch) or 'per_op'
+      want_g     the fused backward also hands out gb, ga (weight gradients);  want_gx: the block input's gradient is wanted
+      wgrads     per weight: take its gradient"""
+    fwd = ops.block_form(dt, blk, W, B, H) if (contiguous and have_frags) else None
+    row = ops.BLOCK_FORMS.get(fwd)
+    trainable = any(w_rg)
+    mask_x = (not first) or bool(mask_input)
+    want_gx = (not first) or bool(need_x_grad)
+    if not train or not (want_gx or trainable):
+        bwd = 'skip'                # (a frozen first block whose input needs no gradient)
+    elif fwd == 'bneck0' and not trainable:
+        bwd = 'chain'
+    elif row is not None and row.nops == 3 and want_gx and (have_xbits or not mask_x):
+        bwd = 'fused'               # (the fused chain masks by the sign bits of the block input: without them, RELU_BITS off, per-op)
+    else:
+        bwd = 'per_op'
+    if row is None:
+        want_ab = True              # (the per-op convolutions write them anyway)
+    elif not row.ab_bits:
+        want_ab = bool(train)       # bneck2: no sign bits of a, b, so it keeps a and b themselves
+    else:
+        # a frozen block keeps only the sign bits of its intermediates; a trainable one a and b as well, for its weight gradients, and so
+        # does an identity block whose fused backward cannot run for want of the input's sign bits
+        want_ab = bool(train) and (trainable or (row.nops == 3 and mask_x and not have_xbits))
+    # the per-op backward reads a and b: it must never follow a forward that did not keep them
+    assert bwd != 'per_op' or want_ab, (fwd, bwd)
+    return BlockPlan(fwd, want_ab, bool(train and relu_bits), mask_x, bwd, bwd == 'fused' and trainable, want_gx,
+                     tuple(bool(r) and bwd in ('fused', 'per_op') for r in w_rg))
+
+
+class _BlockRec(object):
+    """what a block's backward needs of its forward.  geom / s / wb: ConvGeom, FrozenBN scale and dgrad operand of conv1, conv2, conv3
+    [, projection]; wt: the fragment-major dgrad operands of a fused forward; ab_bits: the sign bits of a, b"""
+    __slots__ = ('plan', 'blk', 'x', 'a', 'b', 'y', 'xbits', 'H', 'W', 'geom', 's', 'wb', 'wt', 'ab_bits')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _block_wgrads(dt, B, r, t, grads, base, batch, gp, gb=None, ga=None):
+    """the weight gradients the plan takes, into grads[base + their place among the block's tensors t]: conv3, conv2, conv1, projection, from
+    the masked output gradient gp and the gradients gb, ga of the two intermediates.  Without gb / ga (per-op backward) the two
+    input-gradient convolutions make them here, each right after the weight gradient that reads the same gradient.  Returns ga"""
+    def wg(k, g, act):
+        if r.plan.wgrads[k]:
+            grads[base + 5 * k] = ops.wgrad(dt, g, act, B, r.geom[k], rowscale=r.s[k], batch=batch, param=t[5 * k])
+    wg(2, gp, r.b)
+    if gb is None:
+        gb = ops.conv_dgrad(dt, gp, B, r.geom[2], r.wb[2], mask=r.b, ldm=r.b.stride(0))
+    wg(1, gb, r.a)
+    if ga is None:
+        ga = ops.conv_dgrad(dt, gb, B, r.geom[1], r.wb[1], mask=r.a, ldm=r.a.stride(0))
+    wg(0, ga, r.x)
+    if r.blk.ds:
+        wg(3, gp, r.x)
+    return ga
+
+
 class StageFn(Function):
     """one ResNet stage (layer1..layer4) of Bottleneck blocks on NHWC tokens.
     per-block tensors: conv1.w, bn1(4), conv2.w, bn2(4), conv3.w, bn3(4) [, ds.conv.w, ds.bn(4)].
@@ -896,89 +970,56 @@ class StageFn(Function):
         # flows into it - and reading the bf16 tensor for that is 16x the bytes (65 MB per layer1 block at B = 64).  Every block's
         # last convolution also writes the sign bits of its output; the next block's backward (or the next stage's, or
         # input_proj's: meta['holder']) reads those.
-        tr = any(ctx.needs_input_grad) and ops.RELU_BITS
+        train = any(ctx.needs_input_grad)
         xbits = meta.get('x_bits')
-        for blk in blocks:
+        for bi_, blk in enumerate(blocks):
+            # 1. operands, once for every form: (wf, wb, scale, bias) and the fragment-major images of conv1, conv2, conv3 [, projection]
             n = 20 if blk.ds else 15
             t = T[i:i + n]
             i += n
             cin, pl = blk.cin, blk.planes
-            w1f, w1b, s1, b1 = _prep_conv(dt, t[0], t[1:5])
-            w2f, w2b, s2, b2 = _prep_conv(dt, t[5], t[6:10])
-            w3f, w3b, s3, b3 = _prep_conv(dt, t[10], t[11:15])
-            g1 = ConvGeom(H, W, cin, pl, 1)
+            prep = [_prep_conv(dt, t[k], t[k + 1:k + 5]) for k in range(0, n, 5)]
             g2 = ConvGeom(H, W, pl, pl, 3, blk.stride, blk.dil, blk.dil)
-            g3 = ConvGeom(g2.Ho, g2.Wo, pl, 4 * pl, 1)
-            if ops.bneck_ok(dt, blk, W, B, H) and x.is_contiguous():
-                # the whole block in one launch, its intermediates never in HBM (csrc/bneck.hip)
-                cf = [packing.lookup_conv_frag(t[k]) for k in (0, 5, 10)]
-                if all(c is not None for c in cf):
-                    # a frozen block (layer1, backbone.py:60-62) keeps only the sign bits of its intermediates: the fused backward
-                    # needs nothing else; a trainable one (layer2) keeps a and b as well, for its weight gradients
-                    frozen = not (t[0].requires_grad or t[5].requires_grad or t[10].requires_grad)
-                    # the fused input-gradient chain needs the sign bits of the block input whenever that gradient is masked; without
-                    # them (RELU_BITS off) the backward is the per-op chain, which reads a and b: keep them then
-                    first_ = blk is blocks[0]
-                    mask_x_ = (not first_) or meta['mask_input']
-                    if mask_x_ and xbits is None:
-                        frozen = False
-                    # (layer3: the launch also touches the NEXT block's operands, so that they are L2-resident when that block streams them)
-                    nx = [packing.lookup_conv_frag(T[i + k]) for k in (0, 5, 10)] if (cin == 1024 and i + 15 <= len(T)) else None
-                    nx = [c[0] for c in nx] if nx and all(c is not None for c in nx) else None
-                    y, a, b, ybits, abits, bbits = ops.bneck_fwd(x, B, H, W, [c[0] for c in cf], ((s1, b1), (s2, b2), (s3, b3)),
-                                                                 train=any(ctx.needs_input_grad), want_bits=bool(tr), want_ab=not frozen, nxt=nx)
-                    saved.append(dict(blk=blk, x=x, a=a, b=b, g1=g1, g2=g2, g3=g3, s=(s1, s2, s3), wb=(w1b, w2b, w3b), H=H, W=W, y=y,
-                                      xbits=xbits, fused=[c[1] for c in cf], ab_bits=(abits, bbits)))
-                    x, xbits = y, ybits
-                    continue
-            if blk.ds and ops.bneck2_ok(dt, blk, W) and x.is_contiguous():
-                # layer2's first block (stride 2), forward in one launch; the per-op backward below finds x, a, b, y as usual
-                wdf, wdb, sd, bd = _prep_conv(dt, t[15], t[16:20])
-                cf = [packing.lookup_conv_frag(t[k]) for k in (0, 5, 10, 15)]
-                if all(c is not None for c in cf):
-                    y, a, b, ybits = ops.bneck2_fwd(x, B, H, [c[0] for c in cf], ((s1, b1), (s2, b2), (s3, b3), (sd, bd)),
-                                                    train=any(ctx.needs_input_grad), want_bits=bool(tr))
-                    saved.append(dict(blk=blk, x=x, a=a, b=b, g1=g1, g2=g2, g3=g3, s=(s1, s2, s3), wb=(w1b, w2b, w3b), H=H, W=W, y=y,
-                                      xbits=xbits, gd=ConvGeom(H, W, cin, 4 * pl, 1, blk.stride), sd=sd, wdb=wdb))
-                    x, H, W, xbits = y, g2.Ho, g2.Wo, ybits
-                    continue
-            if blk.ds and ops.bneck0_ok(dt, blk, W) and x.is_contiguous():
-                # layer1's first block, forward in one launch (the backward below is the per-op one: it finds x, a, b, y as usual)
-                wdf, wdb, sd, bd = _prep_conv(dt, t[15], t[16:20])
-                cf = [packing.lookup_conv_frag(t[k]) for k in (0, 5, 10, 15)]
-                if all(c is not None for c in cf):
-                    frozen = not any(t[k].requires_grad for k in (0, 5, 10, 15))
-                    y, a, b, ybits, abits, bbits = ops.bneck0_fwd(x, B, H, [c[0] for c in cf], ((s1, b1), (s2, b2), (s3, b3), (sd, bd)),
-                                                                  train=any(ctx.needs_input_grad), want_bits=bool(tr), want_ab=not frozen)
-                    saved.append(dict(blk=blk, x=x, a=a, b=b, g1=g1, g2=g2, g3=g3, s=(s1, s2, s3), wb=(w1b, w2b, w3b), H=H, W=W, y=y,
-                                      xbits=xbits, gd=ConvGeom(H, W, cin, 4 * pl, 1, blk.stride), sd=sd, wdb=wdb,
-                                      chain=[c[1] for c in cf] if frozen else None, ab_bits=(abits, bbits)))
-                    x, xbits = y, ybits
-                    continue
-            a = ops.conv_fwd(dt, x, B, g1, w1f, scale=s1, bias=b1, act=ACT_RELU)
-            b = ops.conv_fwd(dt, a, B, g2, w2f, scale=s2, bias=b2, act=ACT_RELU)
-            rec = dict(blk=blk, x=x, a=a, b=b, g1=g1, g2=g2, g3=g3, s=(s1, s2, s3), wb=(w1b, w2b, w3b), H=H, W=W)
+            geom = [ConvGeom(H, W, cin, pl, 1), g2, ConvGeom(g2.Ho, g2.Wo, pl, 4 * pl, 1)]
             if blk.ds:
-                wdf, wdb, sd, bd = _prep_conv(dt, t[15], t[16:20])
-                gd = ConvGeom(H, W, cin, 4 * pl, 1, blk.stride)
-                idn = ops.conv_fwd(dt, x, B, gd, wdf, scale=sd, bias=bd)
-                rec.update(gd=gd, sd=sd, wdb=wdb)
+                geom.append(ConvGeom(H, W, cin, 4 * pl, 1, blk.stride))
+            cf = [packing.lookup_conv_frag(t[k]) for k in range(0, n, 5)]
+            fragged = all(c is not None for c in cf)
+            # 2. the plan: forward form, what to keep, backward form
+            plan = block_plan(dt, blk, B, H, W, bi_ == 0, meta['mask_input'], x.is_contiguous(), xbits is not None, train,
+                              ctx.needs_input_grad[0], [t[k].requires_grad for k in range(0, n, 5)], fragged, ops.RELU_BITS)
+            rec = _BlockRec(plan=plan, blk=blk, x=x, xbits=xbits, H=H, W=W, geom=geom, s=[q[2] for q in prep], wb=[q[1] for q in prep])
+            # 3. the launch(es)
+            if plan.fwd is not None:
+                # the whole block in one launch, its intermediates never in HBM unless kept (csrc/bneck.hip, bneck3.hip)
+                # (layer3: the launch also touches the NEXT block's operands, so that they are L2-resident when that block streams them)
+                nx = [packing.lookup_conv_frag(T[i + k]) for k in (0, 5, 10)] if (plan.fwd == 'bneck3' and i + 15 <= len(T)) else None
+                nx = [c[0] for c in nx] if nx and all(c is not None for c in nx) else None
+                y, rec.a, rec.b, ybits, *rec.ab_bits = ops.block_fwd(plan.fwd, x, B, H, W, [c[0] for c in cf], [(q[2], q[3]) for q in prep],
+                                                                     train=train, want_bits=plan.want_bits, want_ab=plan.want_ab, nxt=nx)
+                rec.wt = [c[1] for c in cf]
             else:
-                idn = x
-            ybits = torch.empty((B * g3.Ho * g3.Wo, g3.Co // 8), device=x.device, dtype=torch.uint8) if (tr and g3.Co % 8 == 0) else None
-            y = ops.conv_fwd(dt, b, B, g3, w3f, scale=s3, bias=b3, res=idn, ldr=idn.stride(0), act=ACT_RELU, act_post_res=1,
-                             **({} if ybits is None else dict(bits_out=ybits)))
-            rec['y'], rec['xbits'] = y, xbits
+                (w1f, _, s1, b1), (w2f, _, s2, b2), (w3f, _, s3, b3) = prep[:3]
+                rec.a = ops.conv_fwd(dt, x, B, geom[0], w1f, scale=s1, bias=b1, act=ACT_RELU)
+                rec.b = ops.conv_fwd(dt, rec.a, B, g2, w2f, scale=s2, bias=b2, act=ACT_RELU)
+                idn = ops.conv_fwd(dt, x, B, geom[3], prep[3][0], scale=prep[3][2], bias=prep[3][3]) if blk.ds else x
+                g3 = geom[2]
+                ybits = (torch.empty((B * g3.Ho * g3.Wo, g3.Co // 8), device=x.device, dtype=torch.uint8)
+                         if (plan.want_bits and g3.Co % 8 == 0) else None)
+                y = ops.conv_fwd(dt, rec.b, B, g3, w3f, scale=s3, bias=b3, res=idn, ldr=idn.stride(0), act=ACT_RELU, act_post_res=1,
+                                 **({} if ybits is None else dict(bits_out=ybits)))
+            # 4. the record
+            rec.y = y
             saved.append(rec)
             x, H, W, xbits = y, g2.Ho, g2.Wo, ybits
         if meta.get('holder') is not None:
             meta['holder']['bits'] = xbits
         ctx.bwd_next = None
         chain = meta.get('chain')
-        if tr and chain is not None:
+        if train and ops.RELU_BITS and chain is not None:
             ctx.bwd_next = chain.top                    # (the stage below: its backward follows this stage's, ops.BackwardChain)
-            if saved and saved[-1].get('fused') is not None:
-                chain.top = tuple(saved[-1]['fused'][:3])      # what this stage's backward streams first: its last block's operands
+            if saved and saved[-1].plan.fwd in ('bneck', 'bneck3'):
+                chain.top = tuple(saved[-1].wt[:3])     # what this stage's backward streams first: its last block's operands
         ctx.saved, ctx.meta, ctx.T = saved, meta, T
         ctx.out_hw = (H, W)
         return x
@@ -989,74 +1030,45 @@ class StageFn(Function):
         dt, B = meta['dt'], meta['B']
         grads = [None] * len(T)
         # incoming gradient is w.r.t. the post-ReLU stage output: mask it (idempotent if the consumer already did)
-        gp = _as(gy, dt) if meta.get('grad_premasked') else ops.relu_mask(dt, _as(gy, dt), saved[-1]['y'])
+        gp = _as(gy, dt) if meta.get('grad_premasked') else ops.relu_mask(dt, _as(gy, dt), saved[-1].y)
         rb = ops.ReduceBatch()
-        i_end = len(T)
-        need_x_grad = ctx.needs_input_grad[0]
+        base = len(T)
         for bi_ in range(len(saved) - 1, -1, -1):
             r = saved[bi_]
-            blk = r['blk']
-            n = 20 if blk.ds else 15
-            base = i_end - n
-            i_end = base
+            plan, g1, w1b = r.plan, r.geom[0], r.wb[0]
+            n = 20 if r.blk.ds else 15
+            base -= n
             t = T[base:base + n]
-            s1, s2, s3 = r['s']
-            w1b, w2b, w3b = r['wb']
-            first = bi_ == 0
-            want_gx = (not first) or need_x_grad
-            if not want_gx and not any(t[k].requires_grad for k in range(0, n, 5)):
-                gp = None               # a frozen first block whose input needs no gradient: nothing to compute (and a fused forward
-                continue                # kept no intermediates for the per-op code below)
-            if r.get('chain') is not None and want_gx:
+            if plan.bwd == 'skip':
+                gp = None
+                continue
+            mask_by_x = dict(mask=r.x, ldm=r.x.stride(0)) if plan.mask_x else {}
+            if plan.bwd == 'chain':
                 # layer1's block 0, frozen: gy -> gb -> ga in one launch (sign bits of b, a from the fused forward), then the input-gradient
                 # GEMMs of the projection and of conv1 (its residual operand); the stem's output needs no mask here (StemFn masks by its own
                 # pooled output)
-                _, _, ga = ops.bneck_bwd(gp, B, r['H'], r['W'], r['chain'], *r['ab_bits'], None, chain_only=True)
-                side = ops.conv_dgrad(dt, gp, B, r['gd'], r['wdb'])
-                mask_x = (not first) or meta['mask_input']
-                ep = (dict(mask=r['x'], ldm=r['x'].stride(0)) if mask_x else {})
-                gp = ops.conv_dgrad(dt, ga, B, r['g1'], w1b, res=side, ldr=side.stride(0), **ep)
+                _, _, ga = ops.bneck_bwd(gp, B, r.H, r.W, r.wt, *r.ab_bits, None, chain_only=True)
+                side = ops.conv_dgrad(dt, gp, B, r.geom[3], r.wb[3])
+                gp = ops.conv_dgrad(dt, ga, B, g1, w1b, res=side, ldr=side.stride(0), **mask_by_x)
                 continue
-            if r.get('fused') is not None and want_gx:
-                mask_x = (not first) or meta['mask_input']
-                if not mask_x or r.get('xbits') is not None:
-                    # the input-gradient chain in one launch; a trainable block (layer2) also takes the two intermediate gradients out
-                    # of it for its three weight-gradient GEMMs (a frozen one - layer1, backbone.py:60-62 - needs neither)
-                    train_w = t[0].requires_grad or t[5].requires_grad or t[10].requires_grad
-                    prev = saved[bi_ - 1] if bi_ > 0 else None          # (the block the backward visits next: its operands, layer3 only)
-                    nx = prev['fused'] if (prev is not None and prev.get('fused') is not None and blk.cin == 1024) else None
-                    gx, gb, ga = ops.bneck_bwd(gp, B, r['H'], r['W'], r['fused'], *r['ab_bits'], r['xbits'] if mask_x else None, want_g=train_w,
-                                               nxt=nx)
-                    if t[10].requires_grad:
-                        grads[base + 10] = ops.wgrad(dt, gp, r['b'], B, r['g3'], rowscale=s3, batch=rb, param=t[10])
-                    if t[5].requires_grad:
-                        grads[base + 5] = ops.wgrad(dt, gb, r['a'], B, r['g2'], rowscale=s2, batch=rb, param=t[5])
-                    if t[0].requires_grad:
-                        grads[base + 0] = ops.wgrad(dt, ga, r['x'], B, r['g1'], rowscale=s1, batch=rb, param=t[0])
-                    gp = gx
-                    continue
-            # conv3 (1x1): wgrad, dgrad masked by relu(b)
-            if t[10].requires_grad:
-                grads[base + 10] = ops.wgrad(dt, gp, r['b'], B, r['g3'], rowscale=s3, batch=rb, param=t[10])
-            gb = ops.conv_dgrad(dt, gp, B, r['g3'], w3b, mask=r['b'], ldm=r['b'].stride(0))
-            # conv2 (3x3): wgrad, dgrad masked by relu(a)
-            if t[5].requires_grad:
-                grads[base + 5] = ops.wgrad(dt, gb, r['a'], B, r['g2'], rowscale=s2, batch=rb, param=t[5])
-            ga = ops.conv_dgrad(dt, gb, B, r['g2'], w2b, mask=r['a'], ldm=r['a'].stride(0))
-            # conv1 (1x1) wgrad
-            if t[0].requires_grad:
-                grads[base + 0] = ops.wgrad(dt, ga, r['x'], B, r['g1'], rowscale=s1, batch=rb, param=t[0])
-            if blk.ds and t[15].requires_grad:
-                grads[base + 15] = ops.wgrad(dt, gp, r['x'], B, r['gd'], rowscale=r['sd'], batch=rb, param=t[15])
-            if want_gx:
+            if plan.bwd == 'fused':
+                # the input-gradient chain in one launch; a trainable block (layer2) also takes the two intermediate gradients out
+                # of it for its three weight-gradient GEMMs (a frozen one - layer1, backbone.py:60-62 - needs neither)
+                prev = saved[bi_ - 1] if bi_ > 0 else None          # (the block the backward visits next: its operands, layer3 only)
+                nx = prev.wt if (prev is not None and plan.fwd == 'bneck3' and prev.plan.fwd == 'bneck3') else None
+                gx, gb, ga = ops.bneck_bwd(gp, B, r.H, r.W, r.wt, *r.ab_bits, r.xbits if plan.mask_x else None, want_g=plan.want_g, nxt=nx)
+                if plan.want_g:
+                    _block_wgrads(dt, B, r, t, grads, base, rb, gp, gb, ga)
+                gp = gx
+                continue
+            # per-op: conv3 (1x1) wgrad, dgrad masked by relu(b); conv2 (3x3) wgrad, dgrad masked by relu(a); conv1 and projection wgrad
+            ga = _block_wgrads(dt, B, r, t, grads, base, rb, gp)
+            if plan.want_gx:
                 # (a stride-2 projection: its input gradient stays on the projection's output grid, ops.proj_dgrad)
-                side, ep_side = ops.proj_dgrad(dt, gp, B, r['gd'], r['wdb']) if blk.ds else (gp, dict(ldr=gp.stride(0)))
-                mask_x = (not first) or meta['mask_input']
-                if mask_x and r.get('xbits') is not None:
-                    ep = dict(mask=r['xbits'], ldm=r['xbits'].stride(0), mask_bits=True)
-                else:
-                    ep = dict(mask=r['x'], ldm=r['x'].stride(0)) if mask_x else {}
-                gp = ops.conv_dgrad(dt, ga, B, r['g1'], w1b, res=side, **ep_side, **ep)
+                side, ep_side = ops.proj_dgrad(dt, gp, B, r.geom[3], r.wb[3]) if r.blk.ds else (gp, dict(ldr=gp.stride(0)))
+                if plan.mask_x and r.xbits is not None:
+                    mask_by_x = dict(mask=r.xbits, ldm=r.xbits.stride(0), mask_bits=True)
+                gp = ops.conv_dgrad(dt, ga, B, g1, w1b, res=side, **ep_side, **mask_by_x)
             else:
                 gp = None
         # the reduce launch that closes this stage touches the weights the stage BELOW streams first in its backward

@@ -5,6 +5,7 @@ libsedt_hip.so on the current torch stream and returns torch tensors allocated w
 allocator.  No arithmetic happens in torch here; torch is device memory + streams only.
 """
 import ctypes as C
+from collections import namedtuple
 
 import os
 import numpy as np
@@ -1268,15 +1269,46 @@ def encoder_attn_ffn_fwd(x, qk, v, kpm, w_o_frag, b_o, gamma2, beta2, w1_frag, b
 FUSED_BNECK = int(_dev_env('SEDT_BNECK', '5'))      # 0 off, 1 layer1's identity blocks, 2 + layer2's, 3 + layer1's block 0, 4 + layer2's block 0 (forward), 5 + layer3's identity blocks
 
 
-def bneck_ok(dtype, blk, W, B=0, H=0):
-    """the fused-Bottleneck envelope: an identity block of layer1 (256/64 on 16 columns) or layer2 (512/128 on 8) (csrc/bneck.hip), or of
-    layer3 (1024/256 on 4 columns, csrc/bneck3.hip) while B * ceil(H / 8) strips cover the chip about once; bf16"""
+# The fused launch forms of a Bottleneck, in the order block_form tries them.  maps: input channels -> (the FUSED_BNECK level the form needs
+# there, planes, map columns); ok: the library's host-side envelope call; nops: operands (3, or 4 with the projection); stride; ab_bits:
+# the launch writes the sign bits of its two intermediates (a form that does not keeps the intermediates themselves when training);
+# kernel: the forward kernel's name in a recording.
+BlockForm = namedtuple('BlockForm', 'maps ok nops stride ab_bits kernel')
+BLOCK_FORMS = {
+    'bneck3': BlockForm({1024: (5, 256, 4)}, lambda lib, g, B, H, dt: lib.sedt_bneck3_ok(*g, B, H, dt), 3, 1, True, 'bneck3_kernel<false>'),
+    'bneck': BlockForm({256: (1, 64, 16), 512: (2, 128, 8)}, lambda lib, g, B, H, dt: lib.sedt_bneck_ok(*g, dt), 3, 1, True,
+                       'bneck_kernel<BG<{0}, {1}, {2}>, false'),
+    'bneck2': BlockForm({256: (4, 128, 16)}, lambda lib, g, B, H, dt: lib.sedt_bneck2_ok(*g, dt), 4, 2, False, 'bneck2_fwd_kernel'),
+    'bneck0': BlockForm({64: (3, 64, 16)}, lambda lib, g, B, H, dt: lib.sedt_bneck0_ok(*g, dt), 4, 1, True, 'bneck0_fwd_kernel'),
+}
+
+
+def block_form(dtype, blk, W, B=0, H=0):
+    """the fused form a Bottleneck takes on a map of B clips x H rows x W columns, or None (the per-op chain): an identity block of layer1
+    (256/64 on 16 columns) or layer2 (512/128 on 8) ('bneck', csrc/bneck.hip), of layer3 (1024/256 on 4) while B * ceil(H / 8) strips cover
+    the chip about once ('bneck3', csrc/bneck3.hip), layer1's block 0 ('bneck0') or layer2's ('bneck2', forward only); bf16"""
     if dtype != BF16:
-        return False
-    lvl = int(FUSED_BNECK)
-    if blk.cin == 1024:
-        return bool(lvl >= 5 and L.load().sedt_bneck3_ok(blk.cin, blk.planes, W, blk.stride, blk.dil, int(blk.ds), B, H, dtype))
-    return bool(lvl >= (1 if blk.cin == 256 else 2) and L.load().sedt_bneck_ok(blk.cin, blk.planes, W, blk.stride, blk.dil, int(blk.ds), dtype))
+        return None
+    g = (blk.cin, blk.planes, W, blk.stride, blk.dil, int(blk.ds))
+    for name, row in BLOCK_FORMS.items():
+        if blk.cin in row.maps and int(FUSED_BNECK) >= row.maps[blk.cin][0] and row.ok(L.load(), g, B, H, dtype):
+            return name
+    return None
+
+
+def fusable_form(blk):
+    """the form whose static geometry (channels, stride, dilation, projection) a block has - the one it takes when the map, the batch and
+    FUSED_BNECK allow - or None: a weight plan lays the operands of these blocks out fragment-major as well"""
+    for name, row in BLOCK_FORMS.items():
+        if (blk.cin in row.maps and blk.planes == row.maps[blk.cin][1] and blk.stride == row.stride and blk.dil == 1
+                and bool(blk.ds) == (row.nops == 4)):
+            return name
+    return None
+
+
+def bneck_ok(dtype, blk, W, B=0, H=0):
+    """the envelope of the fused identity block, either way (block_form 'bneck' / 'bneck3')"""
+    return block_form(dtype, blk, W, B, H) in ('bneck', 'bneck3')
 
 
 BNECK_PREFETCH = _dev_env('SEDT_BNECK_PREFETCH', '1') != '0'
@@ -1286,38 +1318,44 @@ def _bneck3_prefetch(nxt):
     return L.prefetch_arg(nxt) if (nxt is not None and BNECK_PREFETCH) else None
 
 
-def bneck_fwd(x, B, H, W, wf, sb, train=True, want_bits=True, want_ab=False, nxt=None):
-    """x [B*H*W, C] bf16 contiguous; wf = the three fragment-major forward operands; sb = ((s1, b1), (s2, b2), (s3, b3)).
-    Returns (y, a, b, ybits, abits, bbits).  Training: the sign bits of the two intermediates (all bneck_bwd needs of them; [M, P/8] bytes)
-    and, on request, the sign bits of y; want_ab: the intermediates themselves as well (the weight-gradient GEMMs of a trainable block)"""
+def block_fwd(form, x, B, H, W, wf, sb, train=True, want_bits=True, want_ab=False, nxt=None):
+    """one Bottleneck forward in one launch.  x [B*H*W, C] bf16 contiguous; wf = the form's 3 or 4 fragment-major forward operands (conv1,
+    conv2, conv3, projection); sb = their (scale, bias) pairs; nxt ('bneck3'): the next block's operands, touched by this launch so that
+    they are L2-resident when that block streams them.  Returns (y, a, b, ybits, abits, bbits), y on the form's output grid.  Training:
+    the sign bits of the two intermediates (all bneck_bwd needs of them; 'bneck2' has none) and, on request, those of y; want_ab: the
+    intermediates themselves as well (what the weight-gradient GEMMs and the per-op backward read)"""
     _dev_check(x)
+    row = BLOCK_FORMS[form]
     M, C = x.shape
-    P = C // 4
-    assert x.is_contiguous() and M == B * H * W
-    y = torch.empty_like(x)
+    assert x.is_contiguous() and M == B * H * W and C in row.maps and W == row.maps[C][2]
+    P = row.maps[C][1]
+    Co, M2 = 4 * P, B * ((H - 1) // row.stride + 1) * (W // row.stride)
+    dev = dict(device=x.device)
+    y = torch.empty((M2, Co), dtype=torch.bfloat16, **dev)
     a = b = bits = abits = bbits = None
     if train:
-        abits = torch.empty((M, P // 8), device=x.device, dtype=torch.uint8)
-        bbits = torch.empty_like(abits)
-        if want_ab:
-            a = torch.empty((M, P), device=x.device, dtype=torch.bfloat16)
-            b = torch.empty_like(a)
+        if row.ab_bits:
+            abits, bbits = torch.empty((M, P // 8), dtype=torch.uint8, **dev), torch.empty((M2, P // 8), dtype=torch.uint8, **dev)
+        if want_ab or not row.ab_bits:
+            a, b = torch.empty((M, P), dtype=torch.bfloat16, **dev), torch.empty((M2, P), dtype=torch.bfloat16, **dev)
         if want_bits:
-            bits = torch.empty((M, C // 8), device=x.device, dtype=torch.uint8)
-    (s1, b1), (s2, b2), (s3, b3) = sb
+            bits = torch.empty((M2, Co // 8), dtype=torch.uint8, **dev)
     if PROFILE is not None:
-        PROFILE_FUSED.append(('bneck3_kernel<false>' if C == 1024 else 'bneck_kernel<BG<%d, %d, %d>, false' % (C, P, W),
-                              2.0 * M * (2 * C * P + 9 * P * P),
-                              M * (2.0 * C * 2 + (C // 8 if bits is not None else 0) + (2 * (P // 8) if abits is not None else 0)
-                                   + (2 * P * 2 if a is not None else 0)) + 2.0 * (2 * C * P + 9 * P * P)))
-    if C == 1024:
-        # (nxt = the next block's three operands: touched by this launch, L2-resident for the next)
-        L.check(L.load().sedt_bneck3_fwd(_p(x), _p(y), _p(wf[0]), _p(wf[1]), _p(wf[2]), _p(s1), _p(b1), _p(s2), _p(b2), _p(s3), _p(b3), _p(a),
-                                         _p(b), _p(abits), _p(bbits), _p(bits), B, H, _bneck3_prefetch(nxt), L.stream_ptr()), 'bneck3_fwd')
-    else:
-        L.check(L.load().sedt_bneck_fwd(_p(x), _p(y), _p(wf[0]), _p(wf[1]), _p(wf[2]), _p(s1), _p(b1), _p(s2), _p(b2), _p(s3), _p(b3), _p(a),
-                                        _p(b), _p(abits), _p(bbits), _p(bits), C, P, W, B, H, L.stream_ptr()), 'bneck_fwd')
+        # (only the identity forms' records count the weights among their bytes)
+        PROFILE_FUSED.append((row.kernel.format(C, P, W), 2.0 * (M * C * P + M2 * (9 * P * P + P * Co + (C * Co if row.nops == 4 else 0))),
+                              M * C * 2.0 + M2 * (Co * 2.0 + (Co // 8 if bits is not None else 0))
+                              + ((M + M2) * (P // 8) if abits is not None else 0) + ((M + M2) * P * 2.0 if a is not None else 0)
+                              + (2.0 * (2 * C * P + 9 * P * P) if row.nops == 3 else 0)))
+    planes = [_p(abits), _p(bbits), _p(bits)] if row.ab_bits else [_p(bits)]
+    dims = {'bneck': (C, P, W, B, H), 'bneck3': (B, H, _bneck3_prefetch(nxt))}.get(form, (B, H))
+    L.check(getattr(L.load(), 'sedt_%s_fwd' % form)(_p(x), _p(y), *[_p(w) for w in wf], *[_p(v) for pair in sb for v in pair], _p(a), _p(b),
+                                                    *planes, *dims, L.stream_ptr()), form + '_fwd')
     return y, a, b, bits, abits, bbits
+
+
+def bneck_fwd(x, B, H, W, wf, sb, train=True, want_bits=True, want_ab=False, nxt=None):
+    """block_fwd of an identity block: 'bneck3' on 1024 channels, else 'bneck'"""
+    return block_fwd('bneck3' if x.shape[1] == 1024 else 'bneck', x, B, H, W, wf, sb, train, want_bits, want_ab, nxt)
 
 
 def bneck_bwd(gy, B, H, W, wt, abits, bbits, xbits, want_g=False, chain_only=False, nxt=None):
@@ -1347,64 +1385,6 @@ def bneck_bwd(gy, B, H, W, wt, abits, bbits, xbits, want_g=False, chain_only=Fal
     L.check(L.load().sedt_bneck_bwd(_p(gy), _p(gx), _p(wt[2]), _p(wt[1]), None if chain_only else _p(wt[0]), _p(abits), _p(bbits),
                                     None if chain_only else _p(xbits), _p(gb), _p(ga), C, C // 4, W, B, H, L.stream_ptr()), 'bneck_bwd')
     return gx, gb, ga
-
-
-def bneck0_ok(dtype, blk, W):
-    """the fused forward of layer1's first Bottleneck (csrc/bneck.hip: 64 -> 64 -> 64 -> 256 with the projection skip, 16 columns), bf16"""
-    return bool(int(FUSED_BNECK) >= 3 and dtype == BF16 and L.load().sedt_bneck0_ok(blk.cin, blk.planes, W, blk.stride, blk.dil, int(blk.ds), dtype))
-
-
-def bneck0_fwd(x, B, H, wf, sb, train=True, want_bits=True, want_ab=False):
-    """x [B*H*16, 64] bf16 contiguous; wf = the fragment-major forward operands of conv1, conv2, conv3 and the projection; sb = their four
-    (scale, bias) pairs.  Returns (y, a, b, ybits); a, b (what the per-op backward reads) and ybits only when training"""
-    _dev_check(x)
-    M = x.shape[0]
-    assert x.is_contiguous() and M == B * H * 16 and x.shape[1] == 64
-    y = torch.empty((M, 256), device=x.device, dtype=torch.bfloat16)
-    a = b = bits = abits = bbits = None
-    if train:
-        abits = torch.empty((M, 8), device=x.device, dtype=torch.uint8)
-        bbits = torch.empty_like(abits)
-        if want_ab:
-            a = torch.empty((M, 64), device=x.device, dtype=torch.bfloat16)
-            b = torch.empty_like(a)
-        if want_bits:
-            bits = torch.empty((M, 32), device=x.device, dtype=torch.uint8)
-    (s1, b1), (s2, b2), (s3, b3), (sd, bd) = sb
-    if PROFILE is not None:
-        PROFILE_FUSED.append(('bneck0_fwd_kernel', 2.0 * M * (64 * 64 + 9 * 64 * 64 + 2 * 64 * 256),
-                              M * (64 * 2.0 + 256 * 2 + (32 if bits is not None else 0) + (16 if abits is not None else 0) + (256 if a is not None else 0))))
-    L.check(L.load().sedt_bneck0_fwd(_p(x), _p(y), _p(wf[0]), _p(wf[1]), _p(wf[2]), _p(wf[3]), _p(s1), _p(b1), _p(s2), _p(b2), _p(s3), _p(b3),
-                                     _p(sd), _p(bd), _p(a), _p(b), _p(abits), _p(bbits), _p(bits), B, H, L.stream_ptr()), 'bneck0_fwd')
-    return y, a, b, bits, abits, bbits
-
-
-def bneck2_ok(dtype, blk, W):
-    """the fused forward of layer2's first Bottleneck (csrc/bneck.hip: 256 -> 128, 3x3 stride 2, -> 512 with the stride-2 projection), bf16"""
-    return bool(int(FUSED_BNECK) >= 4 and dtype == BF16 and L.load().sedt_bneck2_ok(blk.cin, blk.planes, W, blk.stride, blk.dil, int(blk.ds), dtype))
-
-
-def bneck2_fwd(x, B, H, wf, sb, train=True, want_bits=True):
-    """x [B*H*16, 256] bf16 contiguous; wf = the fragment-major forward operands of conv1, conv2, conv3 and the projection; sb = their four
-    (scale, bias) pairs.  Returns (y [B*H2*8, 512], a [B*H*16, 128], b [B*H2*8, 128], ybits); a, b, ybits only when training"""
-    _dev_check(x)
-    M = x.shape[0]
-    assert x.is_contiguous() and M == B * H * 16 and x.shape[1] == 256
-    M2 = B * ((H - 1) // 2 + 1) * 8
-    y = torch.empty((M2, 512), device=x.device, dtype=torch.bfloat16)
-    a = b = bits = None
-    if train:
-        a = torch.empty((M, 128), device=x.device, dtype=torch.bfloat16)
-        b = torch.empty((M2, 128), device=x.device, dtype=torch.bfloat16)
-        if want_bits:
-            bits = torch.empty((M2, 64), device=x.device, dtype=torch.uint8)
-    (s1, b1), (s2, b2), (s3, b3), (sd, bd) = sb
-    if PROFILE is not None:
-        PROFILE_FUSED.append(('bneck2_fwd_kernel', 2.0 * (M * 256 * 128 + M2 * (9 * 128 * 128 + 128 * 512 + 256 * 512)),
-                              M * 256 * 2.0 + M2 * (512 * 2.0 + (64 if bits is not None else 0)) + ((M + M2) * 128 * 2.0 if a is not None else 0)))
-    L.check(L.load().sedt_bneck2_fwd(_p(x), _p(y), _p(wf[0]), _p(wf[1]), _p(wf[2]), _p(wf[3]), _p(s1), _p(b1), _p(s2), _p(b2), _p(s3), _p(b3),
-                                     _p(sd), _p(bd), _p(a), _p(b), _p(bits), B, H, L.stream_ptr()), 'bneck2_fwd')
-    return y, a, b, bits
 
 
 SLAB_HEADS = _dev_env('SEDT_SLAB_HEADS', '1') != '0'

@@ -125,12 +125,13 @@ class SEDT(nn.Module):
                         lin.append(getattr(self, name).weight)
                 if hasattr(self, 'feature_align'):
                     lin += [m.weight for m in self.feature_align.layers]
-                # identity Bottlenecks of layer1 / layer2 / layer3 run as one fused kernel each way (csrc/bneck.hip, bneck3.hip): their
-                # packed operands fragment-major too
-                cfr = [w for layer in (body.layer1, body.layer2, body.layer3) for b in layer if b.downsample is None
-                       for w in (b.conv1.weight, b.conv2.weight, b.conv3.weight)]
-                for b0 in (body.layer1[0], body.layer2[0]):     # the two projection blocks: fused forwards (bneck0 / bneck2_fwd_kernel)
-                    cfr += [b0.conv1.weight, b0.conv2.weight, b0.conv3.weight, b0.downsample[0].weight]
+                # Bottlenecks that can run as one fused kernel (ops.BLOCK_FORMS): their packed operands fragment-major too, the
+                # three-operand (identity) blocks first, then the blocks with a projection
+                fus = [(b, ops.BLOCK_FORMS.get(ops.fusable_form(b.cfg))) for layer in (body.layer1, body.layer2, body.layer3, body.layer4)
+                       for b in layer]
+                cfr = [w for b, row in fus if row and row.nops == 3 for w in (b.conv1.weight, b.conv2.weight, b.conv3.weight)]
+                cfr += [w for b, row in fus if row and row.nops == 4
+                        for w in (b.conv1.weight, b.conv2.weight, b.conv3.weight, b.downsample[0].weight)]
                 if ops.IGEMM_BREG:                              # developer A/B: B through registers in the LDS-DMA GEMMs of layer3 block 0 / layer4
                     have = set(id(w) for w in cfr)
                     cfr += [w for w, _ in convs if id(w) not in have and id(w) in l34]

@@ -6,8 +6,8 @@ must take there.  Families (the host entry point the row calls; its kernel):
   l1      ops.bneck_fwd / bneck_bwd, C 256 P 64 W 16     bneck_kernel<BG<256, 64, 16>, BWD, SKIP3>   layer1 identity block, H = 125
   l2      ops.bneck_fwd / bneck_bwd, C 512 P 128 W 8     bneck_kernel<BG<512, 128, 8>, BWD>          layer2 identity block, H = 63
   l3      ops.bneck_fwd / bneck_bwd, C 1024 P 256 W 4    bneck3_kernel<BWD>                          layer3 identity block, H = 32
-  b0      ops.bneck0_fwd                                 bneck0_fwd_kernel                           layer1 block 0, H = 125
-  b2      ops.bneck2_fwd                                 bneck2_fwd_kernel                           layer2 block 0, H = 125 -> 63
+  b0      ops.block_fwd('bneck0', ...)                   bneck0_fwd_kernel                           layer1 block 0, H = 125
+  b2      ops.block_fwd('bneck2', ...)                   bneck2_fwd_kernel                           layer2 block 0, H = 125 -> 63
   stem    ops.stem_pool_fwd / stem_pool_wgrad            stem_pool_fwd_kernel, stem_pool_wgrad_kernel   H = 500 / 496 input frames
   c64     ops.conv_fwd / conv_dgrad (3x3, 64 -> 64, W 16)   conv3x3_c64_kernel                       layer1 conv2, H = 125
 

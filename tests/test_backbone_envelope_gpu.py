@@ -227,9 +227,8 @@ def test_first_block_forward(env, case):
     which, Ci, P, C = (2, 256, 128, 512) if s2 else (1, 64, 64, 256)
     _, _, blocks = _layer(which)
     blk = blocks[0]
-    ok = ops.bneck2_ok if s2 else ops.bneck0_ok
-    assert ok(ops.BF16, blk['cfg'], 16) and not ok(ops.BF16, blocks[1]['cfg'], 16 if not s2 else 8)
     assert case.path == ('bneck2' if s2 else 'bneck0')
+    assert ops.block_form(ops.BF16, blk['cfg'], 16) == case.path and ops.block_form(ops.BF16, blocks[1]['cfg'], 16 if not s2 else 8) != case.path
     H2, W2 = ((H - 1) // 2 + 1, 8) if s2 else (H, 16)
     gen = _gen(case.name)
     x = _act(case, H * 16, Ci, gen)
@@ -238,17 +237,18 @@ def test_first_block_forward(env, case):
     def fwd(**kw):
         poison()
         with L.launch_log() as log:
-            r = (ops.bneck2_fwd if s2 else ops.bneck0_fwd)(x, B, H, blk['wf'], blk['sb'], **kw)
+            r = ops.block_fwd(case.path, x, B, H, 16, blk['wf'], blk['sb'], **kw)
             torch.cuda.synchronize()
         assert log[entry] == 1 and sum(log.values()) == 1, dict(log)
         return r
 
     if s2:
-        y, a, b, bits = fwd()
+        y, a, b, bits, abits, bbits = fwd()
+        assert abits is None and bbits is None
         assert y.shape[0] == B * H2 * 8 and a.shape[0] == B * H * 16 and b.shape[0] == B * H2 * 8
-        y1, a1, b1, bits1 = fwd(want_bits=False)
+        y1, a1, b1, bits1, _, _ = fwd(want_bits=False)
         assert bits1 is None and torch.equal(y1, y) and torch.equal(a1, a) and torch.equal(b1, b)
-        y2, a2, _, bits2 = fwd(train=False)
+        y2, a2, _, bits2, _, _ = fwd(train=False)
         assert a2 is None and bits2 is None and torch.equal(y2, y)
     else:
         y, a, b, bits, abits, bbits = fwd(want_ab=True)

@@ -206,15 +206,15 @@ def test_fused_first_block_forward_against_torch(B, H):
     g = torch.Generator().manual_seed(2)
     x = (0.7 * torch.randn(B * H * 16, 64, generator=g)).cuda().bfloat16().relu()
     ws = (blk.conv1.weight, blk.conv2.weight, blk.conv3.weight, blk.downsample[0].weight)
-    assert ops.bneck0_ok(ops.BF16, blk.cfg, 16) and not ops.bneck0_ok(ops.BF16, layer[1].cfg, 16)
+    assert ops.block_form(ops.BF16, blk.cfg, 16) == 'bneck0' and ops.block_form(ops.BF16, layer[1].cfg, 16) != 'bneck0'
     with plan:
         cf = [packing.lookup_conv_frag(w) for w in ws]
         sb = [packing.lookup(w)[2:] for w in ws]
-        y, a, b, bits, abits, bbits = ops.bneck0_fwd(x, B, H, [c[0] for c in cf], sb, want_ab=True)
+        y, a, b, bits, abits, bbits = ops.block_fwd('bneck0', x, B, H, 16, [c[0] for c in cf], sb, want_ab=True)
         for t_, tb in ((a, abits), (b, bbits)):
             w_ = (t_.float() > 0).view(-1, 8, 8).to(torch.uint8)
             assert torch.equal(tb, (w_ << torch.arange(8, device='cuda', dtype=torch.uint8)).sum(-1).to(torch.uint8))
-        y2, a2, b2, bits2, _, _ = ops.bneck0_fwd(x, B, H, [c[0] for c in cf], sb, train=False)
+        y2, a2, b2, bits2, _, _ = ops.block_fwd('bneck0', x, B, H, 16, [c[0] for c in cf], sb, train=False)
         torch.cuda.synchronize()
     assert torch.equal(y, y2) and a2 is None and bits2 is None
     want = (y.float() > 0).view(-1, 32, 8).to(torch.uint8)
@@ -251,14 +251,14 @@ def test_fused_layer2_first_block_forward_against_torch(B, H):
     g = torch.Generator().manual_seed(B * 10 + H)
     x = (0.5 * torch.randn(B * H * 16, 256, generator=g)).cuda().bfloat16().relu()
     ws = (blk.conv1.weight, blk.conv2.weight, blk.conv3.weight, blk.downsample[0].weight)
-    assert ops.bneck2_ok(ops.BF16, blk.cfg, 16) and not ops.bneck2_ok(ops.BF16, layer[1].cfg, 8)
+    assert ops.block_form(ops.BF16, blk.cfg, 16) == 'bneck2' and ops.block_form(ops.BF16, layer[1].cfg, 8) != 'bneck2'
     with plan:
         cf = [packing.lookup_conv_frag(w) for w in ws]
         sb = [packing.lookup(w)[2:] for w in ws]
-        y, a, b, bits = ops.bneck2_fwd(x, B, H, [c[0] for c in cf], sb)
-        y2, a2, b2, bits2 = ops.bneck2_fwd(x, B, H, [c[0] for c in cf], sb, train=False)
+        y, a, b, bits, abits, bbits = ops.block_fwd('bneck2', x, B, H, 16, [c[0] for c in cf], sb)
+        y2, a2, b2, bits2, _, _ = ops.block_fwd('bneck2', x, B, H, 16, [c[0] for c in cf], sb, train=False)
         torch.cuda.synchronize()
-    assert torch.equal(y, y2) and a2 is None and bits2 is None
+    assert torch.equal(y, y2) and a2 is None and bits2 is None and abits is None and bbits is None
     want = (y.float() > 0).view(-1, 64, 8).to(torch.uint8)
     assert torch.equal(bits, (want << torch.arange(8, device='cuda', dtype=torch.uint8)).sum(-1).to(torch.uint8))
     H2 = (H - 1) // 2 + 1

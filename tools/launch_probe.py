@@ -3,7 +3,10 @@
 a launch): the lib.launch_log() counter of one step in bf16 and in f32 with GEMM_X3 (bf16x3), and of one recorded step (ops.PROFILE = [])
 the (dtype code, shape tuple, hint) of every entry plus the fused-Bottleneck records.  Model and inputs as bench.py's C2.
 
-usage:  python tools/launch_probe.py <checkout root> <output .json>       (run it once per checkout, compare the two files)
+The peak of torch's allocator over the logged step goes into the file too: an intermediate kept or dropped by mistake moves it.
+
+usage:  python tools/launch_probe.py <checkout root> <output .json> [batch size, default 64] [frozen]
+        (run it once per checkout, compare the two files; `frozen` builds the model with lr_backbone = 0)
 """
 import json
 import os
@@ -18,13 +21,14 @@ from sound_event_detection_transformer_amd.engine import build_optimizer, train_
 from sound_event_detection_transformer_amd.utilities.synthetic import seeded_state_dict, synthetic_batch
 assert os.path.abspath(ops.__file__).startswith(root), ops.__file__
 dev = torch.device('cuda', 0)
-B, T = 64, 500
-out = {'root': root, 'has_conv_form': hasattr(ops, 'conv_form')}
+B, T = (int(sys.argv[3]) if len(sys.argv) > 3 else 64), 500
+frozen = 'frozen' in sys.argv[4:]
+out = {'root': root, 'B': B, 'frozen': frozen, 'has_conv_form': hasattr(ops, 'conv_form'), 'has_block_plan': hasattr(ops, 'block_form')}
 
 
 def setup(mode):
     runtime.set_compute_dtype(mode)
-    model, criterion, _ = build_model(default_args(enc_layers=3, num_queries=10, dec_at=True, dropout=0.1))
+    model, criterion, _ = build_model(default_args(enc_layers=3, num_queries=10, dec_at=True, dropout=0.1, **(dict(lr_backbone=0.0) if frozen else {})))
     model.load_state_dict(seeded_state_dict(model.state_dict(), 2020))
     model.to(dev).train()
     criterion.to(dev)
@@ -38,9 +42,11 @@ for mode in ('bf16', 'bf16x3'):
     for _ in range(2):
         train_step(model, criterion, opt, x, targets, None, slice(B), max_norm=0.1)
     torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
     with L.launch_log() as log:
         loss, _ = train_step(model, criterion, opt, x, targets, None, slice(B), max_norm=0.1)
     torch.cuda.synchronize()
+    out['max_memory_allocated_' + mode] = torch.cuda.max_memory_allocated()
     out['launches_' + mode] = dict(sorted(log.items()))
     out['loss_' + mode] = float(loss)
     ops.PROFILE = []
@@ -55,4 +61,6 @@ for mode in ('bf16', 'bf16x3'):
     out['fused_' + mode] = [list(f) for f in ops.PROFILE_FUSED]
     del model, criterion, opt
 json.dump(out, open(dst, 'w'), indent=0)
-print('probe', root, {k: (sum(v.values()) if k.startswith('launches') else len(v)) for k, v in out.items() if isinstance(v, (dict, list))})
+print('probe', root, 'B', B, 'frozen', frozen,
+      {k: (sum(v.values()) if k.startswith('launches') else len(v) if isinstance(v, list) else v) for k, v in out.items()
+       if k.split('_')[0] in ('launches', 'recorded', 'fused', 'loss', 'max')})
