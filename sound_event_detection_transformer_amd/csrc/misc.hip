@@ -1164,6 +1164,7 @@ extern "C" int sedt_dropout_grad(const void* in, int64_t ldi, void* out, int64_t
                                  uint32_t seed, const uint32_t* seed_ptr, int dtype, void* stream) {
   SEDT_REQUIRE(p >= 0.f && p < 1.f, "dropout_grad: p out of range");
   long n = (long)rows * cols;
+  if (n == 0) return 0;                 // an empty tensor: nothing to launch (a grid of 0 blocks is a launch error)
   uint32_t th = drop_threshold(p);
   float ik = 1.f / (1.f - p);
   BY_DTYPE(dtype,
@@ -1176,6 +1177,7 @@ extern "C" int sedt_dropout_grad(const void* in, int64_t ldi, void* out, int64_t
 
 extern "C" int sedt_add(const void* a, const void* b, void* out, int rows, int cols, int b_mod, int dtype, void* stream) {
   long n = (long)rows * cols;
+  if (n == 0) return 0;
   BY_DTYPE(dtype,
            hipLaunchKernelGGL(add_kernel<float>, dim3(nblk(n)), dim3(256), 0, S(stream), (const float*)a, (const float*)b,
                               (float*)out, rows, cols, b_mod),
@@ -1192,12 +1194,14 @@ extern "C" int sedt_add_n(const void* const* srcs, int n, void* out, int64_t num
   a.n = n;
   for (int i = 0; i < n; ++i) SEDT_REQUIRE(a.p[i] != nullptr, "add_n: null source %d", i);
   const long n8 = numel / 8;
+  if (n8 == 0) return 0;
   BY_DTYPE(dtype, hipLaunchKernelGGL(add_n_kernel<float>, dim3(nblk(n8)), dim3(256), 0, S(stream), a, (float*)out, n8),
            hipLaunchKernelGGL(add_n_kernel<bf16_t>, dim3(nblk(n8)), dim3(256), 0, S(stream), a, (bf16_t*)out, n8));
   return check_launch("add_n");
 }
 
 extern "C" int sedt_cast(const void* in, int in_dtype, void* out, int out_dtype, int64_t n, void* stream) {
+  if (n == 0) return 0;
   dim3 g(nblk(n)), b(256);
   if (in_dtype == SEDT_F32 && out_dtype == SEDT_BF16)
     hipLaunchKernelGGL((cast_kernel<float, bf16_t>), g, b, 0, S(stream), (const float*)in, (bf16_t*)out, (long)n);
@@ -1233,8 +1237,10 @@ extern "C" int sedt_spsedt_dec_in(const void* patch, const float* query, const f
                                   int P, int qpp, int D, int train, float ratio, uint32_t seed, const uint32_t* seed_ptr, int dtype,
                                   void* stream) {
   SEDT_REQUIRE(patch && query && out && B > 0 && Q > 0 && P > 0 && qpp > 0 && (Q + qpp - 1) / qpp <= P, "spsedt_dec_in: bad arguments");
-  SEDT_REQUIRE(D % 8 == 0 && ((uintptr_t)patch & 15) == 0 && ((uintptr_t)query & 15) == 0 && ((uintptr_t)out & 15) == 0,
-               "spsedt_dec_in: D must be a multiple of 8 and the pointers 16-byte aligned");
+  // patch / out move as VecT<T, 8>: 16 bytes in bf16, 32 in f32; the f32 query rows as float4
+  const uintptr_t va = dtype == SEDT_F32 ? 31 : 15;
+  SEDT_REQUIRE(D % 8 == 0 && ((uintptr_t)patch & va) == 0 && ((uintptr_t)query & 15) == 0 && ((uintptr_t)out & va) == 0,
+               "spsedt_dec_in: D must be a multiple of 8, query 16-byte and patch / out %d-byte aligned", (int)va + 1);
   const uint32_t th = (train && !keep_in && ratio > 0.f) ? drop_threshold(ratio < 1.f ? ratio : 0.99999f) : 0u;
   const int rows = B * Q;
   BY_DTYPE(dtype,
@@ -1263,6 +1269,7 @@ extern "C" int sedt_gelu_fwd(const void* h, void* a, int64_t n, float p, uint32_
   const uint32_t th = p > 0.f ? drop_threshold(p) : 0u;
   const float ik = 1.f / (1.f - p);
   const long n8 = n / 8;
+  if (n8 == 0) return 0;
   BY_DTYPE(dtype,
            hipLaunchKernelGGL(gelu_fwd_kernel<float>, dim3(nblk(n8)), dim3(256), 0, S(stream), (const float*)h, (float*)a, n8, th, ik, seed, seed_ptr),
            hipLaunchKernelGGL(gelu_fwd_kernel<bf16_t>, dim3(nblk(n8)), dim3(256), 0, S(stream), (const bf16_t*)h, (bf16_t*)a, n8, th, ik, seed, seed_ptr));
@@ -1277,6 +1284,7 @@ extern "C" int sedt_gelu_bwd(const void* g, const void* h, void* out, int64_t n,
   const uint32_t th = p > 0.f ? drop_threshold(p) : 0u;
   const float ik = 1.f / (1.f - p);
   const long n8 = n / 8;
+  if (n8 == 0) return 0;
   BY_DTYPE(dtype,
            hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(nblk(n8)), dim3(256), 0, S(stream), (const float*)g, (const float*)h, (float*)out, n8, th, ik, seed, seed_ptr),
            hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3(nblk(n8)), dim3(256), 0, S(stream), (const bf16_t*)g, (const bf16_t*)h, (bf16_t*)out, n8, th, ik, seed, seed_ptr));
@@ -1284,6 +1292,7 @@ extern "C" int sedt_gelu_bwd(const void* g, const void* h, void* out, int64_t n,
 }
 
 extern "C" int sedt_relu_mask(const void* g, const void* y, void* out, int64_t n, int dtype, void* stream) {
+  if (n == 0) return 0;
   BY_DTYPE(dtype,
            hipLaunchKernelGGL(relu_mask_kernel<float>, dim3(nblk(n)), dim3(256), 0, S(stream), (const float*)g, (const float*)y,
                               (float*)out, (long)n),
@@ -1293,6 +1302,7 @@ extern "C" int sedt_relu_mask(const void* g, const void* y, void* out, int64_t n
 }
 
 extern "C" int sedt_sigmoid_grad(const float* g, const float* s, float* out, int64_t n, void* stream) {
+  if (n == 0) return 0;
   hipLaunchKernelGGL(sigmoid_grad_kernel, dim3(nblk(n)), dim3(256), 0, S(stream), g, s, out, (long)n);
   return check_launch("sigmoid_grad");
 }
@@ -1399,6 +1409,7 @@ extern "C" int sedt_maxpool_bwd_y(const void* dy, const uint8_t* idx, const void
 
 extern "C" int sedt_avgpool(const void* x, float* out, int B, int P, int C, int dtype, void* stream) {
   long n = (long)B * C;
+  if (n == 0) return 0;
   if ((C & 7) == 0 && (reinterpret_cast<uintptr_t>(x) & 31) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
     const long n8 = n / 8;
     BY_DTYPE(dtype,
@@ -1424,6 +1435,7 @@ extern "C" int sedt_posenc(const uint8_t* mask, void* pos, int B, int H, int W, 
 
 extern "C" int sedt_mask_resize(const uint8_t* in, uint8_t* out, int B, int Hin, int Win, int Hout, int Wout, void* stream) {
   long n = (long)B * Hout * Wout;
+  if (n == 0) return 0;
   hipLaunchKernelGGL(mask_resize_kernel, dim3(nblk(n)), dim3(256), 0, S(stream), in, out, B, Hin, Win, Hout, Wout);
   return check_launch("mask_resize");
 }

@@ -15,6 +15,7 @@
 namespace sedt {
 
 constexpr int SK_MAXN = 16;
+constexpr size_t SK_LDS_MAX = 160 * 1024;       // LDS of one gfx950 workgroup
 
 template <typename T>
 __global__ __launch_bounds__(256) void skinny_fwd_kernel(const T* __restrict__ x, long ldx, const float* __restrict__ w,
@@ -196,8 +197,19 @@ using namespace sedt;
 
 extern "C" int sedt_skinny_linear_fwd(const void* x, int64_t ldx, const float* w, const float* bias, void* y, int64_t ldy, int M,
                                       int N, int K, int act, int out_f32, int dtype, void* stream) {
-  SEDT_REQUIRE(x && w && y && M > 0 && N >= 1 && N <= SK_MAXN && K >= 8 && K <= 1024, "skinny_linear_fwd: bad arguments (N <= 16, K <= 1024)");
+  SEDT_REQUIRE(x && w && y && M > 0 && N >= 1 && N <= SK_MAXN && K >= 8 && K <= 1024 && K % 4 == 0,
+               "skinny_linear_fwd: bad arguments (N <= 16, K <= 1024, a multiple of 4: LDS rows are read as float4)");
   const size_t lds = (size_t)(N + 16) * (K + 4) * sizeof(float);
+  SEDT_REQUIRE(lds <= SK_LDS_MAX, "skinny_linear_fwd: %zu bytes of LDS exceed the 160 KB of a workgroup", lds);
+  SEDT_REQUIRE(dtype == SEDT_F32 || dtype == SEDT_BF16, "skinny_linear_fwd: unsupported dtype %d", dtype);
+  // the tile passes 64 KB from N = 16, K = 512 on: the launch needs the kernel's dynamic-LDS limit raised
+  static bool attr[2] = {false, false};
+  if (!attr[dtype == SEDT_BF16]) {
+    const void* fn = dtype == SEDT_F32 ? reinterpret_cast<const void*>(skinny_fwd_kernel<float>) : reinterpret_cast<const void*>(skinny_fwd_kernel<bf16_t>);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS_MAX);
+    if (e != hipSuccess) { set_error("skinny_linear_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 1; }
+    attr[dtype == SEDT_BF16] = true;
+  }
   dim3 grid((M + 15) / 16), block(256);
   if (dtype == SEDT_F32)
     hipLaunchKernelGGL(skinny_fwd_kernel<float>, grid, block, lds, SS(stream), (const float*)x, (long)ldx, w, bias, y, (long)ldy, M, N, K,

@@ -57,43 +57,69 @@ def _pool_ref(logits, boxes, attn, mode, q0):
 @pytest.mark.parametrize('mode', MODES)
 @pytest.mark.parametrize('q0,Q,B', [(1, 10, 5), (0, 20, 3), (1, 63, 2)])
 def test_pool_at_kernels_against_torch(mode, q0, Q, B):
+    _pool_at_case(mode, q0, Q, B)
+
+
+# queries past the 128 threads of the block; classes past them (64,604 B of LDS in the attention backward: (31 * 131 + 3 * 31 * 130) * 4);
+# one query, one class; rows behind the window (Qs = q0 + Q + 3), whose gradients are zero.  Reference in float64.
+EDGE_ROWS = [(1, 129, 2, 10, 0), (0, 130, 1, 10, 0), (1, 31, 2, 130, 0), (0, 1, 3, 10, 0), (1, 5, 2, 1, 0), (1, 10, 2, 10, 3)]
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('q0,Q,B,C,tail', EDGE_ROWS)
+def test_pool_at_kernels_at_thread_and_lds_edges(mode, q0, Q, B, C, tail):
+    _pool_at_case(mode, q0, Q, B, C, tail, torch.float64)
+
+
+def _pool_at_case(mode, q0, Q, B, C=10, tail=0, ref_dtype=torch.float32):
     from sound_event_detection_transformer_amd import ops
-    C = 10
+    Qs = q0 + Q + tail
     gen = torch.Generator().manual_seed(1000 + 7 * Q + q0)
-    logits = torch.randn(B, q0 + Q, C + 1, generator=gen) * 2.0
-    boxes = torch.rand(B, q0 + Q, 2, generator=gen) * 0.3
+    logits = torch.randn(B, Qs, C + 1, generator=gen) * 2.0
+    boxes = torch.rand(B, Qs, 2, generator=gen) * 0.3
     attn = torch.randn(B, Q, C, generator=gen) * 3.0
-    # corner cases: two queries with identical logits that hold the maximum of class 2 (max: the FIRST gets the gradient) ...
-    logits[0, q0 + 3] = logits[0, q0 + 1]
-    logits[0, q0 + 1, 2] = logits[0, q0 + 3, 2] = 9.0
-    # ... a clip whose weighted sum exceeds 1 for class 4 (clip: no gradient there) ...
-    logits[1, q0:, 4] = 8.0
-    boxes[1, q0:, 1] = 0.9
-    # ... and attention logits so peaked that the other classes fall under the 1e-7 clamp (no gradient through the clamp)
-    attn[0, 0, :] = -30.0
-    attn[0, 0, 5] = 30.0
+    tie, over = Q >= 4 and C > 2, B >= 2 and C > 4 and Q >= 4           # (over: a few queries at length 0.9 pass 1)
+    if tie:
+        # corner cases: two queries with identical logits that hold the maximum of class 2 (max: the FIRST gets the gradient) ...
+        logits[0, q0 + 3] = logits[0, q0 + 1]
+        logits[0, q0 + 1, 2] = logits[0, q0 + 3, 2] = 9.0
+    if over:
+        # ... a clip whose weighted sum exceeds 1 for class 4 (clip: no gradient there) ...
+        logits[1, q0:q0 + Q, 4] = 8.0
+        boxes[1, q0:q0 + Q, 1] = 0.9
+    if C > 5:
+        # ... and attention logits so peaked that the other classes fall under the 1e-7 clamp (no gradient through the clamp)
+        attn[0, 0, :] = -30.0
+        attn[0, 0, 5] = 30.0
     g = torch.randn(B, C, generator=gen)
-    lr, br, ar = logits.clone().requires_grad_(True), boxes.clone().requires_grad_(True), attn.clone().requires_grad_(True)
-    ref = _pool_ref(lr, br, ar, mode, q0)
-    ref.backward(g)
+    lr, br, ar = (t.to(ref_dtype).requires_grad_(True) for t in (logits, boxes, attn))
+    ref = _pool_ref(lr[:, :q0 + Q], br[:, :q0 + Q], ar, mode, q0)
+    ref.backward(g.to(ref_dtype))
+    ref = ref.float()
+    glr, gbr, gar = (None if t.grad is None else t.grad.float() for t in (lr, br, ar))
     dl, db, da = logits.cuda(), boxes.cuda(), attn.cuda()
     out = ops.pool_at(dl, db if mode == 'weighted_sum' else None, da if mode == 'attn' else None, mode, q0, Q)
     torch.testing.assert_close(out.cpu(), ref.detach(), rtol=2e-6, atol=1e-7)
     gl, gb, ga = ops.pool_at_bwd(dl, db if mode == 'weighted_sum' else None, da if mode == 'attn' else None, mode, q0, Q, g.cuda())
-    torch.testing.assert_close(gl.cpu(), lr.grad, rtol=2e-5, atol=2e-7)
+    torch.testing.assert_close(gl.cpu(), glr, rtol=2e-5, atol=2e-7)
     if q0:
         assert gl[:, 0].abs().max().item() == 0.0                 # the audio-tag query takes no part
     if mode == 'weighted_sum':
-        torch.testing.assert_close(gb.cpu(), br.grad, rtol=2e-5, atol=2e-7)
-        assert gb[1, q0:, 1].abs().max().item() > 0 and float(out[1, 4]) == 1.0
+        torch.testing.assert_close(gb.cpu(), gbr, rtol=2e-5, atol=2e-7)
+        if over:
+            assert gb[1, q0:q0 + Q, 1].abs().max().item() > 0 and float(out[1, 4]) == 1.0
+        if tail:
+            assert gb[:, q0 + Q:].abs().max().item() == 0.0
     else:
         assert gb is None
     if mode == 'attn':
-        torch.testing.assert_close(ga.cpu(), ar.grad, rtol=2e-5, atol=2e-7)
+        torch.testing.assert_close(ga.cpu(), gar, rtol=2e-5, atol=2e-7)
     else:
         assert ga is None
-    if mode == 'max':                                            # tie: all of class 2's gradient of clip 0 went through query 1
-        assert lr.grad[0, q0 + 3].abs().max().item() == 0.0 or Q == 0
+    if tail:                                                     # rows behind the window: written, and zero
+        assert gl[:, q0 + Q:].abs().max().item() == 0.0
+    if mode == 'max' and tie:                                    # tie: all of class 2's gradient of clip 0 went through query 1
+        assert glr[0, q0 + 3].abs().max().item() == 0.0 or Q == 0
         assert gl[0, q0 + 3].abs().max().item() == 0.0
 
 
