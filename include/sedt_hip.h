@@ -48,6 +48,9 @@
  *   sedt_recording_psds_counts                                                no counterpart: PSDS confusion counts from those lists
  *   sedt_cut_clips                                                            no counterpart as a kernel: training windows and their
  *                                                                             target tables cut from recordings on the device
+ *   sedt_bank_stats / sedt_soundscape                                         no counterpart as a kernel: training soundscapes mixed from
+ *                                                                             a sound bank on the device, targets merged per class
+ *                                                                             as data_utils/collapse_event.py merges annotations
  *   sedt_mixup_plan                                                           mixup_data's label half  utilities/mixup.py:30-127
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
@@ -1203,6 +1206,69 @@ int sedt_cut_clips(const float* flat, int64_t flat_len, const int64_t* rec_off, 
                    const int32_t* pick_rec, const int64_t* pick_start, int B, int64_t window, int sr, const int32_t* ev_off,
                    const double* ev_on, const double* ev_end, const int32_t* ev_cls, const double* ev_pmax, int n_events, int max_targets,
                    double min_event_seconds, float* wave, void* blob, int32_t* status, void* stream);
+/* sedt_bank_stats (staging half of "Soundscapes synthesized on the device"): the energy and the peak of every
+ * source of a sound bank - flat f32 [flat_len], source s = flat[src_off[s] .. src_off[s] + src_len[s]), src_off / src_len int64 [n_src]
+ * (clamped to flat_len before they index anything).  sumsq float64 [n_src] = the sum of x * x, every square and every addition in
+ * float64; peak f32 [n_src] = max |x| (0 for an empty source; a NaN sample leaves the peak alone and makes sumsq NaN).  One workgroup
+ * of 256 per source: thread t adds elements t, t + 256, ... in that order, then a fixed tree over the 256 partial sums - no atomics,
+ * so two calls give the same bits.  No allocation, no synchronisation; capturable.  n_src < 1, flat_len < 0 or a null pointer:
+ * non-zero with a message before a pointer is touched. */
+int sedt_bank_stats(const float* flat, int64_t flat_len, const int64_t* src_off, const int64_t* src_len, int n_src, double* sumsq,
+                    float* peak, void* stream);
+/* sedt_soundscape (no counterpart as a kernel: the reference trains on soundscapes mixed and annotated offline - URBAN-SED, DESED's
+ * synthetic subset - whose annotations data_utils/collapse_event.py merged per class; DESIGN.md section 4, "Soundscapes synthesized on
+ * the device"): a training batch of B clips of `window` samples MIXED from a bank of isolated sounds and background recordings that
+ * live on the device, and the clips' target tables, in ONE call.
+ * Inputs: the bank as for sedt_bank_stats; bg [B] and ev [ev_off[B]] DEVICE records, clip b's events ev[ev_off[b] .. ev_off[b + 1])
+ * in plan order (ev_off int32 [B + 1]; at least one ev record allocated).
+ * wave f32 [B][window], float32 with every operation rounded on its own (no contraction).  For sample t of clip b:
+ *   acc = bg.gain * src[(bg.start + t) mod len] of source bg.src - a background shorter than the window loops; bg.src == -1: acc = 0;
+ *   for every event k of the clip in plan order with onset <= t < e_k = min(onset + n, window), i = t - onset:
+ *     acc = acc + ((gain * w(i)) * src[src_start + i]),  w(i) = min(w_in, w_out),
+ *     w_in = i < fade ? float((double)(i + 1) / (double)(fade + 1)) : 1, w_out = n - 1 - i < fade ? float((double)(n - i) /
+ *     (double)(fade + 1)) : 1 (linear ramps of `fade` samples at both ends; float64 divisions, only inside a ramp; fade < 0 is 0);
+ *   peak[b] = max over t of |acc|; scale[b] = peak[b] > peak_limit ? float((double)peak_limit / (double)peak[b]) : 1;
+ *   wave[b][t] = acc * scale[b], acc itself when the scale is 1.
+ * targets: every valid event gives (cls, onset, e_k) in samples.  collapse != 0: the events of one class, sorted by (onset, end), are
+ *   merged - an event whose onset <= the running end of its predecessor joins it and the end becomes the maximum (touching events
+ *   included: data_utils/collapse_event.py collapse), on the integer sample grid.  Then sedt_cut_clips' float64 box formula with
+ *   a = onset / sr, z = end / sr, W = window / sr: kept iff z - a > 0 and z - a >= min_event_seconds; label cls (int64), box
+ *   (float32(((a + z) * 0.5) / W), float32((z - a) / W)); the kept ones in the order (onset, end, cls).
+ * blob: exactly sedt_cut_clips' (8-byte aligned, 8 B + 16 + 16 B max_targets bytes; every clip strong).
+ * status int32 [B]: 0; 1 more than max_targets kept events - the first max_targets are written; 2 (it wins over 1) a record of the
+ *   clip is not inside the bank: an event with src outside 0 .. n_src - 1, src_start < 0, n < 0, src_start + n > the source's length or
+ *   onset < 0; a background with src outside -1 .. n_src - 1 or start outside [0, length); or a clip with more than SEDT_SCAPE_MAXEV
+ *   events (the first SEDT_SCAPE_MAXEV are used).  Such an event or background contributes nothing and yields no target.
+ * Nothing is read out of range: sources are clamped to flat_len; ev_off[B] is clamped to 0 .. SEDT_SCAPE_MAXEV * B and every clip's
+ * range to it.  part f32 [B][ceil(window / SEDT_SCAPE_CHUNK)] is scratch.
+ * Two kernels behind one another on `stream`: (1) workgroup 0 owns the targets (one walk over the batch in tiles of
+ * consecutive clips: a tile's events resolved one per thread, one wave per clip merges and orders in registers, the survivors so
+ * far are the next tile's offset), B * ceil(window / SEDT_SCAPE_CHUNK) more mix one chunk each - 16-byte stores on the destination's boundaries, 16-byte loads
+ * where a source address allows them - and write the chunk's max |acc| to part; (2) one workgroup per chunk reduces its clip's row of
+ * part, the first writes peak / scale, and the chunk is rescaled only when scale != 1.  A maximum has no order: no floating-point
+ * atomics, the bits depend on the clip's records alone.  No allocation, no synchronisation; capturable.
+ * Envelope: 1 <= B <= SEDT_SCAPE_MAXB, 1 <= max_targets <= 63, 1 <= window < 2^31, sr >= 1, n_src >= 1; outside it, with a NaN
+ * min_event_seconds or peak_limit, peak_limit <= 0 or a null pointer, the call returns non-zero with a message before it touches a
+ * pointer. */
+#define SEDT_SCAPE_MAXB 1024
+#define SEDT_SCAPE_MAXEV 63
+#define SEDT_SCAPE_CHUNK 2048
+typedef struct {
+  int32_t src, cls;                 /* source index into the bank; class index */
+  int64_t src_start, n, onset;      /* samples src_start .. src_start + n - 1 of the source are laid at sample `onset` of the clip */
+  float gain;
+  int32_t fade;                     /* samples of the linear ramp at both ends */
+} SedtScapeEvent;                   /* 40 bytes; sedt_sizeof index 13 */
+typedef struct {
+  int32_t src, pad;                 /* source index, -1: no background */
+  int64_t start;                    /* the background's sample under sample 0 of the clip */
+  float gain;
+  int32_t pad2;
+} SedtScapeBg;                      /* 24 bytes; sedt_sizeof index 14 */
+int sedt_soundscape(const float* flat, int64_t flat_len, const int64_t* src_off, const int64_t* src_len, int n_src,
+                    const SedtScapeBg* bg, const SedtScapeEvent* ev, const int32_t* ev_off, int B, int64_t window, int sr,
+                    int max_targets, double min_event_seconds, int collapse, float peak_limit, float* wave, float* part, float* peak,
+                    float* scale, void* blob, int32_t* status, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

@@ -1025,7 +1025,12 @@ def train_on_recordings(step, clips, transform, steps, batch_size=None, split=No
     (np.random on the host), ONE sedt_cut_clips launch for the windows and their target tables, mel, transform, with mix-up the host
     draws and ONE sedt_mixup_plan launch, one replay - nothing is read back inside the loop.  The statuses of the cuts and of the plans
     are logged on the device and checked ONCE at the end: a clip with more events than max_targets raises, naming step and recording.
-    Returns the last step's (total, losses): the stepper's static tensors."""
+    Returns the last step's (total, losses): the stepper's static tensors.
+    ``clips`` may as well be a utilities.soundscape.SoundscapeClips with its bank staged (without ``split``): the loop uses only
+    ``clips.draw(B)``, ``clips.batch(transform, picks, status=)``, ``clips.dev`` and ``targets.names``, and a SoundscapeClips answers
+    them with a drawn plan and ONE sedt_soundscape call that mixes the B clips and builds their tables in the same layout - every step
+    then trains on soundscapes nobody has heard before.  Its statuses mean the same (1: over max_targets; 2: a record outside the
+    bank, which a drawn plan never holds) and every clip is named 'soundscape'."""
     B = int(step.static_x.shape[0]) if batch_size is None else int(batch_size)
     if split is not None and int(split[0]) + int(split[1]) != B:
         raise ValueError(f'train_on_recordings: split {tuple(split)} is not the batch size {B}')

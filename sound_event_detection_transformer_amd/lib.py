@@ -17,6 +17,9 @@ I16 = 3               # sedt_mel_spectrogram and sedt_resample only: the wavefor
 RESAMPLE_BLK = 1024   # sedt_resample: outputs per workgroup (SEDT_RESAMPLE_BLK)
 RESAMPLE_DESC_WORDS = 6
 CLIPS_MAXB = 1024      # sedt_cut_clips: clips per launch (SEDT_CLIPS_MAXB)
+SCAPE_MAXB = 1024      # sedt_soundscape: clips per call (SEDT_SCAPE_MAXB)
+SCAPE_MAXEV = 63       # sedt_soundscape: events per clip (SEDT_SCAPE_MAXEV)
+SCAPE_CHUNK = 2048     # sedt_soundscape: samples per mixing workgroup (SEDT_SCAPE_CHUNK)
 GEMM_X3 = False       # runtime.set_compute_dtype('bf16x3'): the f32 mode's contractions go through the BF16X3 code
 
 
@@ -219,6 +222,8 @@ SIGNATURES = {
     'sedt_resample_ok': (_i, [_i, _i, _i, _i, _i, _i64]),
     'sedt_resample': (_i, [_vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _i64, _vp]),
     'sedt_cut_clips': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _i64, _i] + [_vp] * 5 + [_i, _i, _d, _vp, _vp, _vp, _vp]),
+    'sedt_bank_stats': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp]),
+    'sedt_soundscape': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _d, _i, _f] + [_vp] * 7),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_mixup_plan': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,311 @@
+"""Training soundscapes synthesized on the device.  Both corpora of the reference (URBAN-SED, DESED's synthetic subset) were made by
+laying isolated foreground sounds over background recordings at drawn onsets and signal-to-noise ratios; the generator wrote the
+annotations and data_utils/collapse_event.py merged them per class.  Here a bank of such sounds is staged on the device ONCE and every
+training batch is a fresh set of soundscapes: the host draws a plan (which sounds, where, how loud), ONE call mixes the B clips and
+builds their target tables (sedt_soundscape, csrc/soundscape.hip) in the layout sedt_cut_clips writes, so DeviceTargets, TargetTables.load
+and load_mixed take them unchanged.  DESIGN.md section 4 ("Soundscapes synthesized on the device") holds the definition;
+tests/soundscape_ref.py restates it.
+
+    scapes = SoundscapeClips(mel, labels, window_seconds=10.0)
+    scapes.add_events(sounds, ['Speech', 'Dog', ...]).add_backgrounds(rooms)
+    x, targets = scapes.batch(transform, scapes.draw(64))        # (B, 1, frames, n_mels), DeviceTargets - nothing synchronises
+    engine.train_on_recordings(step, scapes, transform, steps)    # the plain loop takes it as it takes a RecordingClips
+
+The plan.  ``draw`` consumes np.random clip by clip, in this order (a seed fixes the plan):
+    background  bi = randint(n_backgrounds), start = randint(len_bg)                   (nothing is drawn with background=False)
+    K = randint(lo, hi + 1) events; for each:  c = randint(number of classes that have sounds) - the c-th such class, ascending;
+        s = randint(sounds of that class); snr = uniform(snr_lo, snr_hi); n = min(len_src, max_event_samples, window);
+        src_start = randint(len_src - n + 1); onset = randint(window - n + 1)
+Gains are computed in float64 and stored as float32: g_bg = 10^(ref_db / 20) / rms_bg (1 for a silent background),
+g_ev = 10^((ref_db + snr) / 20) / rms_src, the RMS taken over the WHOLE source - an RMS reference, not a loudness (LUFS) one as
+Scaper's.  fade = round(fade_seconds * sr) samples of linear ramp at both ends of an event.
+
+``draw_plan``, ``make_plan``, ``gains`` and the record dtypes are the host half and need no GPU."""
+import math
+
+import numpy as np
+import torch
+
+from .. import lib as L
+from .recording import stage_recordings, stage_resampled
+from .recording_clips import DeviceTargets, blob_layout
+from .transforms import PinnedRing
+
+# the device records of sedt_soundscape (include/sedt_hip.h: SedtScapeEvent 40 bytes, SedtScapeBg 24 bytes; sedt_sizeof 13 and 14)
+EVENT = np.dtype([('src', '<i4'), ('cls', '<i4'), ('src_start', '<i8'), ('n', '<i8'), ('onset', '<i8'), ('gain', '<f4'), ('fade', '<i4')])
+BACKGROUND = np.dtype([('src', '<i4'), ('pad', '<i4'), ('start', '<i8'), ('gain', '<f4'), ('pad2', '<i4')])
+STATUS_REASONS = {1: 'more events survive in the clip than max_targets holds: build SoundscapeClips with a larger max_targets',
+                  2: 'a record of the clip does not lie inside the bank (or the clip holds more than 63 events)'}
+
+
+class SoundscapePlan(object):
+    """the records of B soundscapes as sedt_soundscape reads them: ``bg`` BACKGROUND [B] (src -1: no background), ``ev`` EVENT [E],
+    ``ev_off`` int32 [B + 1] - clip b's events are ev[ev_off[b]:ev_off[b + 1]], mixed in that order"""
+
+    def __init__(self, bg, ev, ev_off):
+        self.bg = np.ascontiguousarray(bg, BACKGROUND)
+        self.ev = np.ascontiguousarray(ev, EVENT)
+        self.ev_off = np.ascontiguousarray(ev_off, np.int32)
+        B = self.bg.shape[0]
+        if self.bg.shape != (B,) or self.ev_off.shape != (B + 1,) or self.ev.ndim != 1:
+            raise ValueError('SoundscapePlan: bg [B], ev [E], ev_off [B + 1]')
+        if self.ev_off[0] != 0 or self.ev_off[-1] != self.ev.shape[0] or bool((np.diff(self.ev_off) < 0).any()):
+            raise ValueError('SoundscapePlan: ev_off is not the exclusive scan of the clips\' event counts')
+        if B and int(np.diff(self.ev_off).max()) > L.SCAPE_MAXEV:
+            raise ValueError(f'SoundscapePlan: a clip holds {int(np.diff(self.ev_off).max())} events, sedt_soundscape takes {L.SCAPE_MAXEV}')
+
+    def __len__(self):
+        return int(self.bg.shape[0])
+
+    def events(self, b):
+        return self.ev[int(self.ev_off[b]):int(self.ev_off[b + 1])]
+
+
+def gains(ref_db, snr_db, rms):
+    """float32(10^((ref_db + snr_db) / 20) / rms) from float64 arithmetic; rms == 0 (a silent background): 1"""
+    rms = float(rms)
+    if rms == 0.0:
+        return np.float32(1.0)
+    return np.float32(np.float64(10.0) ** ((np.float64(ref_db) + np.float64(snr_db)) / np.float64(20.0)) / np.float64(rms))
+
+
+def check_bank_stats(what, sumsq, classes):
+    """refuse what sedt_bank_stats found in newly staged sources: a non-finite sum of squares (a NaN or infinite sample) and a
+    foreground sound (class >= 0) without energy; a silent background (class -1) is allowed"""
+    for i, (q, c) in enumerate(zip(sumsq, classes)):
+        if not math.isfinite(q):
+            raise ValueError(f'SoundscapeClips.{what}: source {i} holds non-finite samples')
+        if c >= 0 and q == 0.0:
+            raise ValueError(f'SoundscapeClips.{what}: source {i} is silent: a foreground sound needs energy to be placed at an SNR')
+
+
+def make_plan(backgrounds, events):
+    """a SoundscapePlan from hand-made records: ``backgrounds`` one entry per clip, None or (src, start, gain); ``events`` one list per
+    clip of (src, cls, src_start, n, onset, gain, fade).  Nothing but the shape and the event count per clip is checked here: a record
+    outside the bank raises the clip's status on the device."""
+    if len(backgrounds) != len(events):
+        raise ValueError('make_plan: one background entry and one event list per clip')
+    bg = np.zeros(len(backgrounds), BACKGROUND)
+    bg['src'] = -1
+    for b, g in enumerate(backgrounds):
+        if g is not None:
+            bg[b]['src'], bg[b]['start'], bg[b]['gain'] = int(g[0]), int(g[1]), np.float32(g[2])
+    rows = [tuple(e) for clip in events for e in clip]
+    ev = np.array(rows, EVENT) if rows else np.zeros(0, EVENT)
+    off = np.concatenate([[0], np.cumsum([len(c) for c in events])]).astype(np.int64)
+    if len(events) and int(np.diff(off).max()) > L.SCAPE_MAXEV:
+        raise ValueError(f'make_plan: a clip holds {int(np.diff(off).max())} events, sedt_soundscape takes {L.SCAPE_MAXEV}')
+    return SoundscapePlan(bg, ev, off.astype(np.int32))
+
+
+def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None,
+              fade_seconds=0.01, background=True):
+    """the plan of B soundscapes (module docstring: the order np.random is consumed in).  lens / rms: samples and float64 RMS per
+    source; by_class: per class the source indices of its sounds; backgrounds: the source indices of the background recordings"""
+    lo, hi = int(n_events[0]), int(n_events[1])
+    if not 0 <= lo <= hi:
+        raise ValueError(f'draw: n_events {tuple(n_events)} is not a range 0 <= lo <= hi')
+    if hi > L.SCAPE_MAXEV:
+        raise ValueError(f'draw: up to {hi} events per clip asked for, sedt_soundscape takes {L.SCAPE_MAXEV}')
+    classes = [c for c, own in enumerate(by_class) if len(own)]
+    if hi > 0 and not classes:
+        raise ValueError('draw: the bank is empty: add_events() first')
+    if background and not len(backgrounds):
+        raise ValueError('draw: no background recording is staged: add_backgrounds() first, or background=False')
+    if int(B) < 1:
+        raise ValueError(f'draw: {B} clips')
+    window = int(window)
+    cap = window if max_event_seconds is None else max(int(round(float(max_event_seconds) * sr)), 1)
+    fade = int(round(float(fade_seconds) * sr))
+    bg = np.zeros(int(B), BACKGROUND)
+    bg['src'] = -1
+    ev, off = [], [0]
+    for b in range(int(B)):
+        if background:
+            s = int(backgrounds[np.random.randint(len(backgrounds))])
+            bg[b]['src'], bg[b]['start'], bg[b]['gain'] = s, np.random.randint(int(lens[s])), gains(ref_db, 0.0, rms[s])
+        for _ in range(np.random.randint(lo, hi + 1)):
+            c = classes[np.random.randint(len(classes))]
+            s = int(by_class[c][np.random.randint(len(by_class[c]))])
+            snr = np.random.uniform(float(snr_db[0]), float(snr_db[1]))
+            n = min(int(lens[s]), cap, window)
+            src_start = np.random.randint(int(lens[s]) - n + 1)
+            onset = np.random.randint(window - n + 1)
+            ev.append((s, c, src_start, n, onset, gains(ref_db, snr, rms[s]), fade))
+        off.append(len(ev))
+    return SoundscapePlan(bg, np.array(ev, EVENT) if ev else np.zeros(0, EVENT), np.asarray(off, np.int32))
+
+
+class SoundscapeClips(object):
+    """mel: the DeviceMelSpectrogram of the model (its sample rate is the bank's after staging); labels: the class names;
+    window_seconds: the clip length; max_targets: the events a clip's tables hold (1 .. 63, the stepper's TargetTables must be built
+    with the same value); min_event_seconds: merged events shorter than this are dropped; collapse: merge the events of one class that
+    overlap or touch, as data_utils/collapse_event.py does for the reference's corpora; peak_limit: a clip whose peak exceeds it is
+    scaled down to it.  See the module docstring."""
+
+    STATUS_REASONS = STATUS_REASONS
+
+    def __init__(self, mel, labels, window_seconds=10.0, max_targets=32, min_event_seconds=0.0, collapse=True, peak_limit=1.0,
+                 device='cuda', resample_quality='kaiser_best'):
+        self.mel, self.labels = mel, list(labels)
+        self.window_seconds = float(window_seconds)
+        self.window = int(round(self.window_seconds * mel.sr))
+        self.max_targets, self.min_event_seconds = int(max_targets), float(min_event_seconds)
+        self.collapse, self.peak_limit = bool(collapse), float(peak_limit)
+        if not 1 <= self.max_targets <= 63:
+            raise ValueError('max_targets must be in 1..63 (the target tables\' own limit)')
+        if not mel.min_samples <= self.window < 2 ** 31:
+            raise ValueError(f'SoundscapeClips: a window of {self.window} samples is outside {mel.min_samples} (what the front end needs) '
+                             '.. 2^31 - 1')
+        if math.isnan(self.min_event_seconds):
+            raise ValueError('SoundscapeClips: min_event_seconds is NaN')
+        if not self.peak_limit > 0.0:
+            raise ValueError(f'SoundscapeClips: peak_limit {peak_limit} is not a number > 0')
+        self.dev = torch.device(device)
+        self.resample_quality, self._resamplers = resample_quality, {}
+        self.ns, self.src_cls = [], []                      # per source: samples, class index (-1: a background recording)
+        self.by_class, self.backgrounds = [[] for _ in self.labels], []
+        self.rms, self.peak = np.zeros(0, np.float64), np.zeros(0, np.float32)
+        self.flat, self.src_off, self.table = None, None, None
+        self.last_peak = self.last_scale = None
+        self._ring, self._buf, self._amp, self._keep = None, {}, {}, []
+
+    # ------------------------------------------------------------------ staging
+    def resampler(self, rate):
+        """the DeviceResampler from ``rate`` to mel.sr, made at first use and kept"""
+        rs = self._resamplers.get(int(rate))
+        if rs is None:
+            from .resample import DeviceResampler
+            rs = self._resamplers[int(rate)] = DeviceResampler(int(rate), self.mel.sr, self.resample_quality, device=self.dev)
+        return rs
+
+    def _class_index(self, label):
+        if isinstance(label, (int, np.integer)) and not isinstance(label, bool):
+            if 0 <= int(label) < len(self.labels):
+                return int(label)
+        elif label in self.labels:
+            return self.labels.index(label)
+        raise ValueError(f'SoundscapeClips.add_events: class {label!r} is not one of the {len(self.labels)} labels')
+
+    def _add(self, what, waves, classes, sample_rates):
+        waves = list(waves)
+        if not waves or len(waves) != len(classes):
+            raise ValueError(f'SoundscapeClips.{what}: at least one source, one class per sound')
+        for i, w in enumerate(waves):
+            if int(w.shape[0]) == 0:
+                raise ValueError(f'SoundscapeClips.{what}: source {i} is empty')
+        if sample_rates is not None:
+            flat, _, ns, keep = stage_resampled(waves, sample_rates, self.resampler, self.dev)
+        else:
+            flat, _, ns, keep = stage_recordings(waves, self.dev)
+        ns = [int(n) for n in ns]
+        if min(ns) < 1:
+            raise ValueError(f'SoundscapeClips.{what}: source {ns.index(min(ns))} is empty')
+        n_old, all_ns = len(self.ns), self.ns + ns
+        joined = flat[:sum(ns)] if self.flat is None else torch.cat([self.flat[:sum(self.ns)], flat[:sum(ns)]])
+        off = np.concatenate([[0], np.cumsum(all_ns)]).astype(np.int64)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        table = {'off': up(off[:-1]), 'len': up(np.asarray(all_ns, np.int64))}
+        # the statistics of the new sources: one launch, read back once per add (staging is not the loop)
+        sumsq = torch.zeros(len(ns), dtype=torch.float64, device=self.dev)
+        peak = torch.zeros(len(ns), dtype=torch.float32, device=self.dev)
+        L.check(L.load().sedt_bank_stats(L.p(joined), int(off[-1]), L.p(table['off'][n_old:]), L.p(table['len'][n_old:]), len(ns),
+                                         L.p(sumsq), L.p(peak), L.stream_ptr()), 'bank_stats')
+        sumsq, peak = sumsq.cpu().numpy(), peak.cpu().numpy()
+        check_bank_stats(what, sumsq, classes)
+        # everything is checked: commit
+        self._keep.append(keep)                                      # the raw input lives until the copies behind it have run
+        self.flat, self.src_off, self.table, self.ns = joined, off, table, all_ns
+        self.src_cls = self.src_cls + list(classes)
+        for i, c in enumerate(classes):
+            (self.by_class[c] if c >= 0 else self.backgrounds).append(n_old + i)
+        self.rms = np.concatenate([self.rms, np.sqrt(sumsq / np.asarray(ns, np.float64))])
+        self.peak = np.concatenate([self.peak, peak])
+        return self
+
+    def add_events(self, waves, event_labels, sample_rates=None):
+        """stage isolated foreground sounds, each with ONE class (a name or an index): 1-D float32 / int16 at mel.sr (host or device)
+        or, with ``sample_rates`` (one int or one per sound), at any rate and interleaved (frames, channels) - down-mixed and resampled
+        on the device as RecordingClips.add does.  Unknown labels, empty, silent and non-finite sounds are refused.  Returns self."""
+        classes = [self._class_index(l) for l in event_labels]
+        return self._add('add_events', waves, classes, sample_rates)
+
+    def add_backgrounds(self, waves, sample_rates=None):
+        """stage background recordings (as add_events; a silent one is allowed and is mixed with gain 1).  Returns self."""
+        waves = list(waves)
+        return self._add('add_backgrounds', waves, [-1] * len(waves), sample_rates)
+
+    def __len__(self):
+        return len(self.ns)
+
+    def wave(self, src):
+        """the device view of one staged source (1-D float32 at mel.sr)"""
+        return self.flat[int(self.src_off[src]):int(self.src_off[src + 1])]
+
+    # ------------------------------------------------------------------ plans
+    def draw(self, B, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None, fade_seconds=0.01, background=True):
+        """the SoundscapePlan of B fresh soundscapes: draw_plan over the staged bank (module docstring)"""
+        if not self.ns:
+            raise ValueError('SoundscapeClips.draw: the bank is empty: add_events() first')
+        return draw_plan(B, self.ns, self.rms, self.by_class, self.backgrounds, self.window, self.mel.sr, n_events, snr_db, ref_db,
+                         max_event_seconds, fade_seconds, background)
+
+    def plan(self, backgrounds, events):
+        """a SoundscapePlan from hand-made records (make_plan); class names in the events' second field are looked up"""
+        events = [[(e[0], self._class_index(e[1]) if isinstance(e[1], str) else e[1]) + tuple(e[2:]) for e in clip] for clip in events]
+        return make_plan(backgrounds, events)
+
+    # ------------------------------------------------------------------ batches
+    def buffers(self, B):
+        """(wave (B, window) f32, blob uint8, status int32 [B], part f32 scratch, peak f32 [B], scale f32 [B]) of batch size B, owned by
+        this object and reused by every mix"""
+        buf = self._buf.get(int(B))
+        if buf is None:
+            chunks = -(-self.window // L.SCAPE_CHUNK)
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)
+            buf = self._buf[int(B)] = (z((B, self.window), torch.float32), z(blob_layout(B, self.max_targets)[3], torch.uint8),
+                                       z(B, torch.int32), z(B * chunks, torch.float32), z(B, torch.float32), z(B, torch.float32))
+        return buf
+
+    def mix(self, plan, status=None):
+        """ONE sedt_soundscape call on the current stream into this object's buffers: (wave (B, window) f32 on the device, samples per
+        clip - the window - as a host list, DeviceTargets).  The records travel through a ring of pinned buffers; nothing synchronises.
+        ``status``: an int32 [B] device tensor to raise the statuses in instead of the buffer's own (a row of a log,
+        engine.train_on_recordings).  ``last_peak`` / ``last_scale`` are the clips' peaks before scaling and their scales, on the device."""
+        if self.table is None:
+            raise RuntimeError('SoundscapeClips.mix: add_events() / add_backgrounds() first')
+        B, E = len(plan), int(plan.ev.shape[0])
+        if not 1 <= B <= L.SCAPE_MAXB:
+            raise ValueError(f'SoundscapeClips.mix: 1 .. {L.SCAPE_MAXB} clips per call')
+        if self._ring is None:
+            self._ring = PinnedRing(self.dev)
+        ev = plan.ev if E else np.zeros(1, EVENT)
+        raw = self._ring.upload(np.concatenate([plan.bg.view(np.uint8), ev.view(np.uint8), plan.ev_off.view(np.uint8)]))
+        n_bg, n_ev = BACKGROUND.itemsize * B, EVENT.itemsize * ev.shape[0]
+        d_bg, d_ev, d_off = raw[:n_bg], raw[n_bg:n_bg + n_ev], raw[n_bg + n_ev:n_bg + n_ev + 4 * (B + 1)]
+        wave, blob, own, part, peak, scale = self.buffers(B)
+        status = own if status is None else status
+        if status.shape != (B,) or status.dtype != torch.int32 or not status.is_contiguous() or status.device != wave.device:
+            raise ValueError('SoundscapeClips.mix: status is a contiguous int32 [B] tensor on the device')
+        L.check(L.load().sedt_soundscape(L.p(self.flat), int(self.src_off[-1]), L.p(self.table['off']), L.p(self.table['len']),
+                                         len(self.ns), L.p(d_bg), L.p(d_ev), L.p(d_off), B, self.window, self.mel.sr, self.max_targets,
+                                         self.min_event_seconds, int(self.collapse), self.peak_limit, L.p(wave), L.p(part), L.p(peak),
+                                         L.p(scale), L.p(blob), L.p(status), L.stream_ptr()), 'soundscape')
+        self.last_peak, self.last_scale = peak, scale
+        return wave, [self.window] * B, DeviceTargets(blob, status, B, self.max_targets, ['soundscape'] * B, self.window_seconds)
+
+    def batch(self, transform, plan=None, B=None, status=None):
+        """mix -> mel -> transform: (x (B, 1, frames, n_mels), DeviceTargets).  ``plan``: a SoundscapePlan, else draw(B).  The transform
+        (a DeviceBoxTransform) may augment; a DeviceViewTransform makes both views of the mean-teacher recipe and the result is
+        ((x_teacher, x_student), DeviceTargets)."""
+        if plan is None:
+            if B is None:
+                raise ValueError('SoundscapeClips.batch: plan= or B=')
+            plan = self.draw(B)
+        wave, lengths, targets = self.mix(plan, status=status)
+        amp = self._amp.get(wave.shape[0])
+        if amp is None:
+            amp = self._amp[wave.shape[0]] = torch.zeros((wave.shape[0], 1 + self.window // self.mel.hop, self.mel.F), dtype=torch.float32,
+                                                         device=self.dev)
+        amp, nframes = self.mel(wave, lengths=lengths, out=amp)
+        return transform(amp, nframes=nframes), targets
