@@ -460,7 +460,11 @@ int sedt_multi_pack(const SedtPackJob* jobs, int njobs, int nblocks, int dtype, 
  * packing: W [N][K] (nn.Linear layout; N % 32 == 0, K % 32 == 0) as 1 KB blocks, block (n / 32, k / 16) at byte
  * ((n / 32) * (K / 16) + k / 16) * 1024, inside it lane l = 32 * ((k % 16) / 8) + n % 32 owns 8 consecutive k (16 bytes).
  * sedt_pack_frag packs any number of f32 master weights into that form (wf) and / or the same form of W^T (wb: the operand of the
- * input-gradient chain) in one launch; nblocks = sum over the jobs of (N / 32) * (K / 32), blk0 = first block of a job. */
+ * input-gradient chain) in one launch; nblocks = sum over the jobs of (N / 32) * (K / 32), blk0 = first block of a job.
+ * Alignment (the jobs are a DEVICE table: the entry point cannot check it): an f32 master is read as float4, so w must be 16-byte
+ * aligned; a bf16 source is read four elements at a time, so w must be 8-byte aligned; wf and wb are written 16 bytes per lane and
+ * must be 16-byte aligned.  PackPlan keeps to this: packed operands start at multiples of 8 elements of a 256-byte aligned buffer, and
+ * an f32 master below 16-byte alignment is not fragment-packed. */
 typedef struct SedtFragJob {
   const float* w; /* f32 master [N][K]; with src_bf16 a bf16 matrix [N][K] (a packed convolution operand of sedt_multi_pack) */
   void* wf;       /* fragment-major W, bf16, or null */

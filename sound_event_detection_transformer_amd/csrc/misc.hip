@@ -1309,13 +1309,19 @@ extern "C" int sedt_sigmoid_grad(const float* g, const float* s, float* out, int
 
 extern "C" int sedt_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale, float* bias,
                             int n, void* stream) {
+  SEDT_REQUIRE(n >= 0, "bn_fold: n = %d", n);
+  if (n == 0) return 0;                                           // (an empty tensor: a grid of 0 blocks is a launch error)
+  SEDT_REQUIRE(w && b && rm && rv && scale && bias, "bn_fold: null pointer");
   hipLaunchKernelGGL(bn_fold_kernel, dim3(nblk(n)), dim3(256), 0, S(stream), w, b, rm, rv, scale, bias, n);
   return check_launch("bn_fold");
 }
 
 extern "C" int sedt_pack_conv(const float* w, int Cout, int Cin, int taps, const float* bnscale, void* wf, void* wb,
                               int dtype, void* stream) {
+  SEDT_REQUIRE(Cout >= 0 && Cin >= 0 && taps >= 0, "pack_conv: Cout = %d, Cin = %d, taps = %d", Cout, Cin, taps);
   long n = (long)Cout * Cin * taps;
+  if (n == 0) return 0;                                           // (an empty tensor: a grid of 0 blocks is a launch error)
+  SEDT_REQUIRE(w, "pack_conv: null pointer");                      // (wf and wb may each be null: that image is not wanted)
   BY_DTYPE(dtype,
            hipLaunchKernelGGL(pack_conv_kernel<float>, dim3(nblk(n)), dim3(256), 0, S(stream), w, Cout, Cin, taps, bnscale,
                               (float*)wf, (float*)wb),

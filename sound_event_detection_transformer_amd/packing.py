@@ -198,7 +198,9 @@ class PackPlan(object):
         self.frag_table, self._fr_params, self._fr_entries = {}, [], []
         self.conv_frag_table, self._cf_entries = {}, []
         self.operand_frag = {}                                        # packed operand pointer (fixed, inside self.wbuf) -> its fragment-major image
-        frags = [w for w in frags if w.dim() == 2 and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0]
+        # (pack_frag_kernel reads an f32 master as float4: a parameter that is a view below 16-byte alignment keeps the per-op chain)
+        frags = [w for w in frags if w.dim() == 2 and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0 and w.is_contiguous()
+                 and w.data_ptr() % 16 == 0]
         packed = {id(w): (wf, wb) for w, wf, wb, _, _ in self._entries}
         conv_frags = [w for w in conv_frags if id(w) in packed and packed[id(w)][0] is not None and packed[id(w)][1] is not None
                       and all(d % 32 == 0 for d in packed[id(w)][0].shape + packed[id(w)][1].shape)]
@@ -260,6 +262,8 @@ class PackPlan(object):
             if len(self._fj):
                 # (the fragment-packed weights are a subset of the linears: a pointer change there changed `key` as well)
                 self._fj['w'] = np.fromiter((w.data_ptr() for w in self._fr_params), np.uint64, len(self._fr_params))
+                if (self._fj['w'][self._fj['src_bf16'] == 0] % 16).any():
+                    raise ValueError('PackPlan: a fragment-packed f32 weight moved to an address below 16-byte alignment')
                 self._host_fj.numpy()[:] = self._fj.view(np.uint8)
                 self._dev_fj.copy_(self._host_fj, non_blocking=True)
                 self.frag_table = {w.data_ptr(): (wf, wb) for w, wf, wb in self._fr_entries}

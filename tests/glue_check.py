@@ -205,14 +205,15 @@ class Kernel(object):
 KERNELS = {}
 
 
-def register(cls):
-    KERNELS[cls.key] = cls()
+def register(cls, table=None):
+    """table: another module's registry (tests/prep_check.py keeps its own, so that each CPU module's table-coverage test sees its own keys)"""
+    (KERNELS if table is None else table)[cls.key] = cls()
     return cls
 
 
-def verify_row(key, c, inp, fr, imgs):
+def verify_row(key, c, inp, fr, imgs, table=None):
     """guards, finiteness and the kernel's own checks on the images (name -> array of the frame's dtype) after a launch or a restatement"""
-    k = KERNELS[key]
+    k = (KERNELS if table is None else table)[key]
     got = {}
     for n, f in fr.items():
         f.check_guard(imgs[n], f'{c["name"]}.{n}')
@@ -227,14 +228,14 @@ def ratio_key(name, c):
     return name if name.startswith('k:') else f'{name} [{c.get("dt", "f32")}]'
 
 
-def restated(key, c, fault=None):
+def restated(key, c, fault=None, table=None):
     """the row through the numpy restatement (with an injected fault, if any) and the same verification as a device result"""
-    k = KERNELS[key]
+    k = (KERNELS if table is None else table)[key]
     inp = k.make(c)
     fr = k.frames(c, inp)
     k.restate(c, inp, fr, fault)
     _generic_fault(fr, fault)
-    return verify_row(key, c, inp, fr, {n: f.buf for n, f in fr.items()})
+    return verify_row(key, c, inp, fr, {n: f.buf for n, f in fr.items()}, table)
 
 
 def _generic_fault(fr, fault):

@@ -16,7 +16,7 @@ the two single-tensor entry points, and - one section, one process - FusedAdamW 
 misaligned slices.  Nothing is skipped and no case is sampled.
 
 Not exercised: multi_adamw_kernel<false>, which only the developer switch SEDT_ADAMW_NT=0 reaches (the library reads it once per
-process); multi_pack, multi_bn_fold and multi_wgrad_reduce have their own tests.
+process); multi_pack, multi_bn_fold and multi_wgrad_reduce have their own tests (tests/test_prep_envelope_gpu.py).
 
 The largest error / bound ratio per kernel and output is printed at the end of the module with -s, with the module's run time.
 The table has NOT been recorded on an MI355X yet (not measured): copy it here from the first device run.  The float32 numpy
