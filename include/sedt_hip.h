@@ -51,6 +51,8 @@
  *   sedt_bank_stats / sedt_soundscape                                         no counterpart as a kernel: training soundscapes mixed from
  *                                                                             a sound bank on the device, targets merged per class
  *                                                                             as data_utils/collapse_event.py merges annotations
+ *   sedt_loudness / sedt_scale_sources                                        no counterpart: ITU-R BS.1770 loudness (K-weighted, gated)
+ *                                                                             of the sources of a bank, and gains applied in place
  *   sedt_mixup_plan                                                           mixup_data's label half  utilities/mixup.py:30-127
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
@@ -1273,6 +1275,41 @@ int sedt_soundscape(const float* flat, int64_t flat_len, const int64_t* src_off,
                     const SedtScapeBg* bg, const SedtScapeEvent* ev, const int32_t* ev_off, int B, int64_t window, int sr,
                     int max_targets, double min_event_seconds, int collapse, float peak_limit, float* wave, float* part, float* peak,
                     float* scale, void* blob, int32_t* status, void* stream);
+/* sedt_loudness (no counterpart in the reference; DESIGN.md section 4, "Loudness (BS.1770) on the device"; tests/loudness_ref.py
+ * restates it): the ITU-R BS.1770-4 programme loudness of every source of a bank, one channel with channel weight 1 - the bank as for
+ * sedt_bank_stats, clamped to flat_len in the same way.  The host finishes: L = -0.691 + 10 log10(zbar) LUFS, -inf for zbar == 0.
+ * coef float64 [10], DEVICE: b0 b1 b2 a1 a2 of the shelf stage, then of the high-pass stage (a0 = 1 dropped).  Each stage is
+ *   transposed direct form II in float64 on the float32 samples widened, from zero state, the shelf first:
+ *   o = b0 v + s0; s0 = b1 v - a1 o + s1; s1 = b2 v - a2 o.  Products and sums may be contracted into FMAs.
+ * hop = H samples (100 ms).  e_h = the sum of y * y over hop h, in sample order.  n >= 4 H: J = n / H - 3 blocks of 4 H samples with
+ *   75 % overlap, z_j = (e_j + e_j+1 + e_j+2 + e_j+3) / (4 H); a trailing partial hop is not used.  n < 4 H has no block in the
+ *   standard: here it is ONE block over all its samples, z_0 = (e_0 + e_1 + ..) / n (0 for n = 0), J = 1, flagged short.
+ * Gates in the z domain: absolute z_j > z_abs (10^((-70 + 0.691) / 10) for the standard's -70 LUFS); relative z_j > 0.1 * (the mean
+ *   of z over the blocks that pass the absolute gate).  zbar float64 [n_src] = the mean of z_j over the blocks that pass both, 0 when
+ *   none does, NaN when a hop energy is not finite (a NaN or infinite sample).  counts int32 [n_src][4] = J, the blocks that pass the
+ *   absolute gate, those that pass both, short (0 / 1).
+ * hop_map float64 [16], DEVICE, row-major [4][4]: the state of the cascade (shelf s0 s1, high-pass s0 s1) after H zero-input samples
+ *   from each unit state - column k from unit state k.  The filter is linear, so the state at the start of hop h + 1 is
+ *   hop_map . (the state at the start of hop h) + (the state hop h leaves when filtered from zero state): the hops are filtered in
+ *   parallel, 256 per round - pass A from zero state, one thread walks the 256 end states into start states and carries the last one
+ *   into the next round, pass B from the true start state sums y * y.  Exact up to rounding (DESIGN quotes the measurement).
+ * work float64 [work_len]: the hop energies; source s owns src_len[s] / H + 1 doubles behind those of the sources before it, so
+ *   work_len >= the sum of (src_len[s] / H + 1).  The lengths live on the device and the call does not synchronise: the entry point
+ *   refuses work_len < n_src, and a source whose range does not fit into work_len is NOT measured - zbar NaN, its four counts -1,
+ *   nothing written outside work (utilities/loudness.py raises on it).
+ * One launch, one workgroup of 256 per source.  The gate passes are fixed-order LDS trees (thread t adds blocks t, t + 256, ...): no
+ * floating-point atomics, two calls give the same bits.  No allocation, no synchronisation; capturable.  n_src < 1, flat_len < 0,
+ * hop < 1, a z_abs that is not a number >= 0, work_len < n_src or a null pointer: non-zero with a message before a pointer is touched. */
+int sedt_loudness(const float* flat, int64_t flat_len, const int64_t* src_off, const int64_t* src_len, int n_src, const double* coef,
+                  const double* hop_map, int hop, double z_abs, double* work, int64_t work_len, double* zbar, int32_t* counts,
+                  void* stream);
+/* sedt_scale_sources: flat[src_off[s] + i] *= gain[s] for every sample of every source (the bank as for sedt_bank_stats, clamped in the
+ * same way; the sources must not overlap), in place and in one launch - the second half of a loudness normalisation.  One float32
+ * multiplication per sample; 16-byte accesses on the 16-byte boundaries of a source, scalar head and tail; a source with gain 1 is
+ * not written at all.  No allocation, no synchronisation; capturable.  n_src < 1, flat_len < 0 or a null pointer: non-zero with a
+ * message before a pointer is touched. */
+int sedt_scale_sources(float* flat, int64_t flat_len, const int64_t* src_off, const int64_t* src_len, int n_src, const float* gain,
+                       void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

@@ -224,6 +224,8 @@ SIGNATURES = {
     'sedt_cut_clips': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _i64, _i] + [_vp] * 5 + [_i, _i, _d, _vp, _vp, _vp, _vp]),
     'sedt_bank_stats': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp]),
     'sedt_soundscape': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _d, _i, _f] + [_vp] * 7),
+    'sedt_loudness': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _d, _vp, _i64, _vp, _vp, _vp]),
+    'sedt_scale_sources': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_mixup_plan': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

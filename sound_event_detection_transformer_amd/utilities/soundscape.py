@@ -17,8 +17,11 @@ The plan.  ``draw`` consumes np.random clip by clip, in this order (a seed fixes
         s = randint(sounds of that class); snr = uniform(snr_lo, snr_hi); n = min(len_src, max_event_samples, window);
         src_start = randint(len_src - n + 1); onset = randint(window - n + 1)
 Gains are computed in float64 and stored as float32: g_bg = 10^(ref_db / 20) / rms_bg (1 for a silent background),
-g_ev = 10^((ref_db + snr) / 20) / rms_src, the RMS taken over the WHOLE source - an RMS reference, not a loudness (LUFS) one as
-Scaper's.  fade = round(fade_seconds * sr) samples of linear ramp at both ends of an event.
+g_ev = 10^((ref_db + snr) / 20) / rms_src, the RMS taken over the WHOLE source - the default, ``level='rms'``.  With ``level='lufs'``
+the reference is the source's BS.1770 loudness L as Scaper's is (utilities/loudness.py, measured on the device when the source is
+staged): 10^(L / 20) stands where the RMS stands, so g = 10^((ref_db + snr - L) / 20), and ref_db and snr are LUFS values.  Nothing
+else changes: the same draws in the same order, the same mixing.  fade = round(fade_seconds * sr) samples of linear ramp at both ends
+of an event.
 
 ``draw_plan``, ``make_plan``, ``gains`` and the record dtypes are the host half and need no GPU."""
 import math
@@ -62,7 +65,8 @@ class SoundscapePlan(object):
 
 
 def gains(ref_db, snr_db, rms):
-    """float32(10^((ref_db + snr_db) / 20) / rms) from float64 arithmetic; rms == 0 (a silent background): 1"""
+    """float32(10^((ref_db + snr_db) / 20) / rms) from float64 arithmetic; rms == 0 (a silent background): 1.  ``rms`` is the source's
+    level as an amplitude: its RMS, or 10^(L / 20) of its loudness L under level='lufs' (0 for -inf)"""
     rms = float(rms)
     if rms == 0.0:
         return np.float32(1.0)
@@ -77,6 +81,15 @@ def check_bank_stats(what, sumsq, classes):
             raise ValueError(f'SoundscapeClips.{what}: source {i} holds non-finite samples')
         if c >= 0 and q == 0.0:
             raise ValueError(f'SoundscapeClips.{what}: source {i} is silent: a foreground sound needs energy to be placed at an SNR')
+
+
+def check_bank_loudness(what, lufs, classes):
+    """refuse a foreground sound (class >= 0) at -inf LUFS - every block under the absolute gate; such a background (class -1) is allowed
+    and mixed with gain 1, as a silent one is"""
+    for i, (l, c) in enumerate(zip(lufs, classes)):
+        if c >= 0 and l == -math.inf:
+            raise ValueError(f'SoundscapeClips.{what}: source {i} lies under the absolute gate (-70 LUFS) in every block: a foreground '
+                             'sound needs a loudness to be placed at an SNR')
 
 
 def make_plan(backgrounds, events):
@@ -100,8 +113,9 @@ def make_plan(backgrounds, events):
 
 def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None,
               fade_seconds=0.01, background=True):
-    """the plan of B soundscapes (module docstring: the order np.random is consumed in).  lens / rms: samples and float64 RMS per
-    source; by_class: per class the source indices of its sounds; backgrounds: the source indices of the background recordings"""
+    """the plan of B soundscapes (module docstring: the order np.random is consumed in).  lens / rms: samples and float64 level per
+    source as an amplitude (the RMS, or 10^(L / 20) under level='lufs'); by_class: per class the source indices of its sounds;
+    backgrounds: the source indices of the background recordings"""
     lo, hi = int(n_events[0]), int(n_events[1])
     if not 0 <= lo <= hi:
         raise ValueError(f'draw: n_events {tuple(n_events)} is not a range 0 <= lo <= hi')
@@ -141,12 +155,13 @@ class SoundscapeClips(object):
     window_seconds: the clip length; max_targets: the events a clip's tables hold (1 .. 63, the stepper's TargetTables must be built
     with the same value); min_event_seconds: merged events shorter than this are dropped; collapse: merge the events of one class that
     overlap or touch, as data_utils/collapse_event.py does for the reference's corpora; peak_limit: a clip whose peak exceeds it is
-    scaled down to it.  See the module docstring."""
+    scaled down to it; level: 'rms' - ref_db and snr_db refer to the sources' RMS - or 'lufs' - to their BS.1770 loudness, measured on
+    the device at staging (``lufs``, ``level_amp`` = 10^(lufs / 20) per source).  See the module docstring."""
 
     STATUS_REASONS = STATUS_REASONS
 
     def __init__(self, mel, labels, window_seconds=10.0, max_targets=32, min_event_seconds=0.0, collapse=True, peak_limit=1.0,
-                 device='cuda', resample_quality='kaiser_best'):
+                 device='cuda', resample_quality='kaiser_best', level='rms'):
         self.mel, self.labels = mel, list(labels)
         self.window_seconds = float(window_seconds)
         self.window = int(round(self.window_seconds * mel.sr))
@@ -161,11 +176,15 @@ class SoundscapeClips(object):
             raise ValueError('SoundscapeClips: min_event_seconds is NaN')
         if not self.peak_limit > 0.0:
             raise ValueError(f'SoundscapeClips: peak_limit {peak_limit} is not a number > 0')
+        if level not in ('rms', 'lufs'):
+            raise ValueError(f"SoundscapeClips: level {level!r} is neither 'rms' nor 'lufs'")
+        self.level, self._loudness = level, None
         self.dev = torch.device(device)
         self.resample_quality, self._resamplers = resample_quality, {}
         self.ns, self.src_cls = [], []                      # per source: samples, class index (-1: a background recording)
         self.by_class, self.backgrounds = [[] for _ in self.labels], []
         self.rms, self.peak = np.zeros(0, np.float64), np.zeros(0, np.float32)
+        self.lufs, self.level_amp = np.zeros(0, np.float64), np.zeros(0, np.float64)       # filled under level='lufs' only
         self.flat, self.src_off, self.table = None, None, None
         self.last_peak = self.last_scale = None
         self._ring, self._buf, self._amp, self._keep = None, {}, {}, []
@@ -211,8 +230,16 @@ class SoundscapeClips(object):
         peak = torch.zeros(len(ns), dtype=torch.float32, device=self.dev)
         L.check(L.load().sedt_bank_stats(L.p(joined), int(off[-1]), L.p(table['off'][n_old:]), L.p(table['len'][n_old:]), len(ns),
                                          L.p(sumsq), L.p(peak), L.stream_ptr()), 'bank_stats')
+        if self.level == 'lufs':                                     # ... and their loudness: one launch more, read back with the rest
+            if self._loudness is None:
+                from .loudness import DeviceLoudness
+                self._loudness = DeviceLoudness(self.mel.sr, self.dev)
+            loud = self._loudness.launch(joined, int(off[-1]), table['off'][n_old:], table['len'][n_old:], ns)
         sumsq, peak = sumsq.cpu().numpy(), peak.cpu().numpy()
         check_bank_stats(what, sumsq, classes)
+        if self.level == 'lufs':
+            lufs = self._loudness.result(*loud, f'SoundscapeClips.{what}').lufs
+            check_bank_loudness(what, lufs, classes)
         # everything is checked: commit
         self._keep.append(keep)                                      # the raw input lives until the copies behind it have run
         self.flat, self.src_off, self.table, self.ns = joined, off, table, all_ns
@@ -221,12 +248,16 @@ class SoundscapeClips(object):
             (self.by_class[c] if c >= 0 else self.backgrounds).append(n_old + i)
         self.rms = np.concatenate([self.rms, np.sqrt(sumsq / np.asarray(ns, np.float64))])
         self.peak = np.concatenate([self.peak, peak])
+        if self.level == 'lufs':
+            self.lufs = np.concatenate([self.lufs, lufs])
+            self.level_amp = np.concatenate([self.level_amp, np.float64(10.0) ** (lufs / np.float64(20.0))])       # (0 for -inf)
         return self
 
     def add_events(self, waves, event_labels, sample_rates=None):
         """stage isolated foreground sounds, each with ONE class (a name or an index): 1-D float32 / int16 at mel.sr (host or device)
         or, with ``sample_rates`` (one int or one per sound), at any rate and interleaved (frames, channels) - down-mixed and resampled
-        on the device as RecordingClips.add does.  Unknown labels, empty, silent and non-finite sounds are refused.  Returns self."""
+        on the device as RecordingClips.add does.  Unknown labels, empty, silent and non-finite sounds are refused, under level='lufs'
+        also a sound at -inf LUFS.  Returns self."""
         classes = [self._class_index(l) for l in event_labels]
         return self._add('add_events', waves, classes, sample_rates)
 
@@ -247,7 +278,8 @@ class SoundscapeClips(object):
         """the SoundscapePlan of B fresh soundscapes: draw_plan over the staged bank (module docstring)"""
         if not self.ns:
             raise ValueError('SoundscapeClips.draw: the bank is empty: add_events() first')
-        return draw_plan(B, self.ns, self.rms, self.by_class, self.backgrounds, self.window, self.mel.sr, n_events, snr_db, ref_db,
+        level = self.level_amp if self.level == 'lufs' else self.rms
+        return draw_plan(B, self.ns, level, self.by_class, self.backgrounds, self.window, self.mel.sr, n_events, snr_db, ref_db,
                          max_event_seconds, fade_seconds, background)
 
     def plan(self, backgrounds, events):
