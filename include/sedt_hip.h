@@ -53,6 +53,8 @@
  *                                                                             as data_utils/collapse_event.py merges annotations
  *   sedt_loudness / sedt_scale_sources                                        no counterpart: ITU-R BS.1770 loudness (K-weighted, gated)
  *                                                                             of the sources of a bank, and gains applied in place
+ *   sedt_stretch / sedt_stretch_workspace / sedt_stretch_ok                   no counterpart: per-event time stretch and pitch shift
+ *                                                                             (phase vocoder, then resampling at a real ratio)
  *   sedt_mixup_plan                                                           mixup_data's label half  utilities/mixup.py:30-127
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
@@ -1310,6 +1312,53 @@ int sedt_loudness(const float* flat, int64_t flat_len, const int64_t* src_off, c
  * message before a pointer is touched. */
 int sedt_scale_sources(float* flat, int64_t flat_len, const int64_t* src_off, const int64_t* src_len, int n_src, const float* gain,
                        void* stream);
+/* sedt_stretch (no counterpart in the reference, whose corpora were generated offline; DESIGN.md section 4, "Pitch shift and time
+ * stretch on the device"; tests/stretch_ref.py restates it in float64): n_jobs excerpts of a bank, each stretched in time by its own
+ * duration factor f and shifted in pitch by its own p semitones - a phase vocoder followed by band-limited resampling at a real ratio.
+ * Job e reads x = flat[src_off .. src_off + n) and writes y = dst[dst_off .. dst_off + m).  With alpha = 2^(p / 12), g = f alpha:
+ *   m = floor(n f + 0.5), m1 = floor(n g + 0.5), r = 1 / g - float64 on the host, carried in the record.
+ *   STFT: N = n_fft, hop = N / 4, periodic Hann window (`window` f32 [N], float64 rounded once), centred with zeros outside [0, n):
+ *     frame t covers samples t hop - N/2 .. t hop + N/2 - 1; T = 1 + n div hop frames of K = N/2 + 1 bins; frames T, T + 1 are zero.
+ *   Vocoder: U = the number of steps u >= 0 with fl64(u r) < T (ceil(T / r) up to the rounding of the product).  s = fl64(u r),
+ *     i = floor(s), a = s - i; mag = (1 - a) |D_i| + a |D_i+1|; S_u = mag exp(i phi_u); phi_0 = arg D_0; phi_u+1 = phi_u + omega_k +
+ *     wrap(arg D_i+1 - arg D_i - omega_k), omega_k = 2 pi hop k / N, wrap(d) = d - 2 pi rint(d / 2 pi), arg 0 = 0.  Magnitudes, angles,
+ *     the phase and its sine and cosine are float64 on the f32 spectrum widened; S is rounded to f32 once.
+ *   Inverse: the inverse real FFT of S_u (the imaginary parts of bins 0 and N/2 dropped) times the window, frame u laid at u hop;
+ *     sample q adds its at most four frames in ascending frame order and is divided by ws[q] = the sum of window^2 over the same
+ *     frames (f32) where ws[q] > 1e-8; z = samples N/2 .. N/2 + m1 - 1 (zero where no frame reaches).
+ *   Resampling: y[i] = sum over j of (s w(s (fl64(i alpha) - j))) z[j], j ascending over 0 <= j < m1, s = min(1, 1 / alpha); w is read
+ *     from `wtab` f32 [512 zero_crossings + 1], wtab[q] = the Kaiser-windowed sinc at q / 512 (float64 rounded once), interpolated
+ *     linearly: pos = |s (t - j)| 512 in float64, q = floor(pos), w = wtab[q] + f32(pos - q) (wtab[q + 1] - wtab[q]); q >= 512
+ *     zero_crossings contributes nothing.  f32 sums.
+ *   r == 1 (g = 1): T = U = 0 and z = x.  alpha == 1: m == m1 and y = z.
+ * twiddle f32 [2][N/2 + 1] is sedt_mel_spectrogram's table.
+ * The records exist twice: jobs_host is read by the entry point (refusals, grid sizes), jobs_dev - the same bytes in DEVICE memory -
+ * by the kernels, which check every record again before they touch memory.
+ * Workspace: the caller's; job e owns floats [ws_off, ws_off + F_e) of it, F_e = 2 T K + 2 U K + U N + m1 rounded up to a multiple
+ *   of 4, laid out  D re [T][K] | D im [T][K] | S re [U][K] | S im [U][K] | windowed inverse frames [U][N] | z [m1].  ws_off is a
+ *   multiple of 4 and the regions follow one another in job order.  sedt_stretch_workspace returns the bytes a job list needs (the
+ *   end of its last region), -1 with a message for a list the entry point would refuse.
+ * status int32 [n_jobs]: 0; 2 the DEVICE record does not lie inside the bank, the destination or the workspace, or is outside the
+ *   envelope - nothing is read or written for it.
+ * Five launches behind one another on `stream` (STFT; vocoder, one thread per job and bin; inverse FFT; overlap-add gather;
+ * resampler), no atomics - the same call gives the same bits; no allocation, no synchronisation; capturable.
+ * Envelope (sedt_stretch_ok): n_fft 512, 1024 or 2048; 1 <= n <= 2^26; alpha in [0.5, 2] (|p| <= 12); f = 1 / (r alpha) in [0.5, 2];
+ *   m, m1, T, U as defined above.  A job outside it, n < 1, regions out of order, a workspace smaller than the list needs, a negative
+ *   count or length, n_jobs > 65535, zero_crossings outside 1 .. 64 or a null pointer: non-zero with a message before anything is
+ *   launched.  n_jobs == 0 returns 0 and launches nothing. */
+typedef struct {
+  int64_t src_off, n;               /* the excerpt: flat[src_off .. src_off + n) */
+  int64_t dst_off, m;               /* the result: dst[dst_off .. dst_off + m) */
+  int64_t m1;                       /* samples between the vocoder and the resampler */
+  double r, alpha;                  /* the vocoder's rate 1 / (f alpha); the resampling ratio 2^(p / 12) */
+  int32_t T, U;                     /* analysis frames; synthesis frames */
+  int64_t ws_off;                   /* the job's first float in the workspace */
+} SedtStretchJob;                   /* 72 bytes; sedt_sizeof index 15 */
+int sedt_stretch_ok(int n_fft, int64_t n, int64_t m, int64_t m1, double r, double alpha, int T, int U);
+int64_t sedt_stretch_workspace(const SedtStretchJob* jobs_host, int n_jobs, int n_fft);
+int sedt_stretch(const float* flat, int64_t flat_len, const SedtStretchJob* jobs_host, const SedtStretchJob* jobs_dev, int n_jobs,
+                 float* dst, int64_t dst_len, void* workspace, int64_t workspace_bytes, const float* window, const float* twiddle,
+                 const float* wtab, int zero_crossings, int n_fft, int32_t* status, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

@@ -20,6 +20,8 @@ CLIPS_MAXB = 1024      # sedt_cut_clips: clips per launch (SEDT_CLIPS_MAXB)
 SCAPE_MAXB = 1024      # sedt_soundscape: clips per call (SEDT_SCAPE_MAXB)
 SCAPE_MAXEV = 63       # sedt_soundscape: events per clip (SEDT_SCAPE_MAXEV)
 SCAPE_CHUNK = 2048     # sedt_soundscape: samples per mixing workgroup (SEDT_SCAPE_CHUNK)
+STRETCH_MAXJOBS = 65535   # sedt_stretch: jobs per call
+STRETCH_TABLE_RES = 512   # sedt_stretch: table points per zero crossing of the resampling filter
 GEMM_X3 = False       # runtime.set_compute_dtype('bf16x3'): the f32 mode's contractions go through the BF16X3 code
 
 
@@ -226,6 +228,9 @@ SIGNATURES = {
     'sedt_soundscape': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _d, _i, _f] + [_vp] * 7),
     'sedt_loudness': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _d, _vp, _i64, _vp, _vp, _vp]),
     'sedt_scale_sources': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp]),
+    'sedt_stretch_ok': (_i, [_i, _i64, _i64, _i64, _d, _d, _i, _i]),
+    'sedt_stretch_workspace': (_i64, [_vp, _i, _i]),
+    'sedt_stretch': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_mixup_plan': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -16,6 +16,13 @@ The plan.  ``draw`` consumes np.random clip by clip, in this order (a seed fixes
     K = randint(lo, hi + 1) events; for each:  c = randint(number of classes that have sounds) - the c-th such class, ascending;
         s = randint(sounds of that class); snr = uniform(snr_lo, snr_hi); n = min(len_src, max_event_samples, window);
         src_start = randint(len_src - n + 1); onset = randint(window - n + 1)
+    With ``pitch_shift=(lo, hi)`` and / or ``time_stretch=(lo, hi)`` (the generator's two event effects; utilities/stretch.py), right
+    after snr and in the generator's order:  p = uniform(pitch range) semitones if pitch_shift is given, then f = uniform(stretch range)
+    if time_stretch is given - both stored as float32 in the plan's ``fx``; n = the largest excerpt whose final length
+    m = floor(n f + 0.5) fits min(len_src f, max_event_samples, window); src_start as above; onset = randint(window - m + 1).  With both
+    None nothing new is drawn: the plan of a seed is the plan it always was.  ``mix`` runs the effects on the device (sedt_stretch)
+    into a buffer behind the bank and hands the unchanged mixing call one more source per transformed event; an event's gain stays
+    what its SOURCE's staged level gives (the level is not measured again after the effect).
 Gains are computed in float64 and stored as float32: g_bg = 10^(ref_db / 20) / rms_bg (1 for a silent background),
 g_ev = 10^((ref_db + snr) / 20) / rms_src, the RMS taken over the WHOLE source - the default, ``level='rms'``.  With ``level='lufs'``
 the reference is the source's BS.1770 loudness L as Scaper's is (utilities/loudness.py, measured on the device when the source is
@@ -37,21 +44,28 @@ from .transforms import PinnedRing
 # the device records of sedt_soundscape (include/sedt_hip.h: SedtScapeEvent 40 bytes, SedtScapeBg 24 bytes; sedt_sizeof 13 and 14)
 EVENT = np.dtype([('src', '<i4'), ('cls', '<i4'), ('src_start', '<i8'), ('n', '<i8'), ('onset', '<i8'), ('gain', '<f4'), ('fade', '<i4')])
 BACKGROUND = np.dtype([('src', '<i4'), ('pad', '<i4'), ('start', '<i8'), ('gain', '<f4'), ('pad2', '<i4')])
+# an event's effects (host only: the device sees SedtStretchJob records, utilities/stretch.py); (0, 1) is the identity
+FX = np.dtype([('semitones', '<f4'), ('factor', '<f4')])
 STATUS_REASONS = {1: 'more events survive in the clip than max_targets holds: build SoundscapeClips with a larger max_targets',
                   2: 'a record of the clip does not lie inside the bank (or the clip holds more than 63 events)'}
 
 
 class SoundscapePlan(object):
     """the records of B soundscapes as sedt_soundscape reads them: ``bg`` BACKGROUND [B] (src -1: no background), ``ev`` EVENT [E],
-    ``ev_off`` int32 [B + 1] - clip b's events are ev[ev_off[b]:ev_off[b + 1]], mixed in that order"""
+    ``ev_off`` int32 [B + 1] - clip b's events are ev[ev_off[b]:ev_off[b + 1]], mixed in that order.  ``fx``: None (no effects) or FX [E],
+    the pitch shift and duration factor of every event; an event's ``n`` is then the length of its EXCERPT, and it occupies
+    floor(n factor + 0.5) samples of the clip from ``onset`` on"""
 
-    def __init__(self, bg, ev, ev_off):
+    def __init__(self, bg, ev, ev_off, fx=None):
         self.bg = np.ascontiguousarray(bg, BACKGROUND)
         self.ev = np.ascontiguousarray(ev, EVENT)
         self.ev_off = np.ascontiguousarray(ev_off, np.int32)
+        self.fx = None if fx is None else np.ascontiguousarray(fx, FX)
         B = self.bg.shape[0]
         if self.bg.shape != (B,) or self.ev_off.shape != (B + 1,) or self.ev.ndim != 1:
             raise ValueError('SoundscapePlan: bg [B], ev [E], ev_off [B + 1]')
+        if self.fx is not None and self.fx.shape != self.ev.shape:
+            raise ValueError('SoundscapePlan: fx [E], one (semitones, factor) per event')
         if self.ev_off[0] != 0 or self.ev_off[-1] != self.ev.shape[0] or bool((np.diff(self.ev_off) < 0).any()):
             raise ValueError('SoundscapePlan: ev_off is not the exclusive scan of the clips\' event counts')
         if B and int(np.diff(self.ev_off).max()) > L.SCAPE_MAXEV:
@@ -94,8 +108,9 @@ def check_bank_loudness(what, lufs, classes):
 
 def make_plan(backgrounds, events):
     """a SoundscapePlan from hand-made records: ``backgrounds`` one entry per clip, None or (src, start, gain); ``events`` one list per
-    clip of (src, cls, src_start, n, onset, gain, fade).  Nothing but the shape and the event count per clip is checked here: a record
-    outside the bank raises the clip's status on the device."""
+    clip of (src, cls, src_start, n, onset, gain, fade) or, with effects, (src, cls, src_start, n, onset, gain, fade, semitones,
+    factor) - the plan has ``fx`` as soon as one event has the two trailing fields, the others are the identity.  Nothing but the
+    shape and the event count per clip is checked here: a record outside the bank raises the clip's status on the device."""
     if len(backgrounds) != len(events):
         raise ValueError('make_plan: one background entry and one event list per clip')
     bg = np.zeros(len(backgrounds), BACKGROUND)
@@ -104,18 +119,46 @@ def make_plan(backgrounds, events):
         if g is not None:
             bg[b]['src'], bg[b]['start'], bg[b]['gain'] = int(g[0]), int(g[1]), np.float32(g[2])
     rows = [tuple(e) for clip in events for e in clip]
-    ev = np.array(rows, EVENT) if rows else np.zeros(0, EVENT)
+    if any(len(e) not in (7, 9) for e in rows):
+        raise ValueError('make_plan: an event is (src, cls, src_start, n, onset, gain, fade) with an optional (semitones, factor) behind')
+    ev = np.array([e[:7] for e in rows], EVENT) if rows else np.zeros(0, EVENT)
+    fx = np.array([e[7:] if len(e) == 9 else (0.0, 1.0) for e in rows], FX) if any(len(e) == 9 for e in rows) else None
     off = np.concatenate([[0], np.cumsum([len(c) for c in events])]).astype(np.int64)
     if len(events) and int(np.diff(off).max()) > L.SCAPE_MAXEV:
         raise ValueError(f'make_plan: a clip holds {int(np.diff(off).max())} events, sedt_soundscape takes {L.SCAPE_MAXEV}')
-    return SoundscapePlan(bg, ev, off.astype(np.int32))
+    return SoundscapePlan(bg, ev, off.astype(np.int32), fx)
+
+
+def is_identity(fx):
+    """bool [E]: the events whose effects are (0 semitones, factor 1) - they are not processed at all"""
+    return (fx['semitones'] == 0.0) & (fx['factor'] == 1.0)
+
+
+def excerpt_for(limit, factor):
+    """the largest n >= 0 with floor(n factor + 0.5) <= limit, in float64 as the stage computes the length"""
+    n = int(math.floor((limit + 0.5) / factor))
+    while n > 0 and math.floor(n * factor + 0.5) > limit:
+        n -= 1
+    while math.floor((n + 1) * factor + 0.5) <= limit:
+        n += 1
+    return n
 
 
 def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None,
-              fade_seconds=0.01, background=True):
+              fade_seconds=0.01, background=True, pitch_shift=None, time_stretch=None):
     """the plan of B soundscapes (module docstring: the order np.random is consumed in).  lens / rms: samples and float64 level per
     source as an amplitude (the RMS, or 10^(L / 20) under level='lufs'); by_class: per class the source indices of its sounds;
-    backgrounds: the source indices of the background recordings"""
+    backgrounds: the source indices of the background recordings; pitch_shift / time_stretch: None or the (lo, hi) range an event's
+    shift in semitones / duration factor is drawn from - with both None nothing new is drawn and the plan has no ``fx``"""
+    effects = pitch_shift is not None or time_stretch is not None
+    if effects:
+        from .stretch import check_effect
+        p_rng = (0.0, 0.0) if pitch_shift is None else (float(pitch_shift[0]), float(pitch_shift[1]))
+        f_rng = (1.0, 1.0) if time_stretch is None else (float(time_stretch[0]), float(time_stretch[1]))
+        for p_, f_ in zip(p_rng, f_rng):
+            check_effect(f_, p_, 'draw')
+        if p_rng[0] > p_rng[1] or f_rng[0] > f_rng[1]:
+            raise ValueError(f'draw: pitch_shift {pitch_shift} / time_stretch {time_stretch} is not a range lo <= hi')
     lo, hi = int(n_events[0]), int(n_events[1])
     if not 0 <= lo <= hi:
         raise ValueError(f'draw: n_events {tuple(n_events)} is not a range 0 <= lo <= hi')
@@ -133,7 +176,7 @@ def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), 
     fade = int(round(float(fade_seconds) * sr))
     bg = np.zeros(int(B), BACKGROUND)
     bg['src'] = -1
-    ev, off = [], [0]
+    ev, fx, off = [], [], [0]
     for b in range(int(B)):
         if background:
             s = int(backgrounds[np.random.randint(len(backgrounds))])
@@ -142,12 +185,23 @@ def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), 
             c = classes[np.random.randint(len(classes))]
             s = int(by_class[c][np.random.randint(len(by_class[c]))])
             snr = np.random.uniform(float(snr_db[0]), float(snr_db[1]))
-            n = min(int(lens[s]), cap, window)
+            n = m = min(int(lens[s]), cap, window)
+            if effects:
+                # the effects as the plan stores them (float32), the lengths from those values as the stage computes them
+                p = np.float32(0.0) if pitch_shift is None else np.float32(np.random.uniform(*p_rng))
+                f = np.float32(1.0) if time_stretch is None else np.float32(np.random.uniform(*f_rng))
+                p, f = np.clip(p, np.float32(p_rng[0]), np.float32(p_rng[1])), np.clip(f, np.float32(f_rng[0]), np.float32(f_rng[1]))
+                n = min(int(lens[s]), excerpt_for(min(cap, window), float(f)))
+                if n < 1:
+                    raise ValueError(f'draw: no excerpt stretched by {float(f)} fits {min(cap, window)} samples')
+                m = int(math.floor(n * float(f) + 0.5))
+                fx.append((p, f))
             src_start = np.random.randint(int(lens[s]) - n + 1)
-            onset = np.random.randint(window - n + 1)
+            onset = np.random.randint(window - m + 1)
             ev.append((s, c, src_start, n, onset, gains(ref_db, snr, rms[s]), fade))
         off.append(len(ev))
-    return SoundscapePlan(bg, np.array(ev, EVENT) if ev else np.zeros(0, EVENT), np.asarray(off, np.int32))
+    return SoundscapePlan(bg, np.array(ev, EVENT) if ev else np.zeros(0, EVENT), np.asarray(off, np.int32),
+                          np.array(fx, FX).reshape(-1) if effects else None)
 
 
 class SoundscapeClips(object):
@@ -156,12 +210,13 @@ class SoundscapeClips(object):
     with the same value); min_event_seconds: merged events shorter than this are dropped; collapse: merge the events of one class that
     overlap or touch, as data_utils/collapse_event.py does for the reference's corpora; peak_limit: a clip whose peak exceeds it is
     scaled down to it; level: 'rms' - ref_db and snr_db refer to the sources' RMS - or 'lufs' - to their BS.1770 loudness, measured on
-    the device at staging (``lufs``, ``level_amp`` = 10^(lufs / 20) per source).  See the module docstring."""
+    the device at staging (``lufs``, ``level_amp`` = 10^(lufs / 20) per source); stretch_n_fft: the frame length of the effects' phase
+    vocoder (512, 1024 or 2048; the resampling filter is ``resample_quality``'s).  See the module docstring."""
 
     STATUS_REASONS = STATUS_REASONS
 
     def __init__(self, mel, labels, window_seconds=10.0, max_targets=32, min_event_seconds=0.0, collapse=True, peak_limit=1.0,
-                 device='cuda', resample_quality='kaiser_best', level='rms'):
+                 device='cuda', resample_quality='kaiser_best', level='rms', stretch_n_fft=2048):
         self.mel, self.labels = mel, list(labels)
         self.window_seconds = float(window_seconds)
         self.window = int(round(self.window_seconds * mel.sr))
@@ -188,6 +243,8 @@ class SoundscapeClips(object):
         self.flat, self.src_off, self.table = None, None, None
         self.last_peak = self.last_scale = None
         self._ring, self._buf, self._amp, self._keep = None, {}, {}, []
+        self.stretch_n_fft, self._stretch, self._fx_buf, self._fx_bank = int(stretch_n_fft), None, None, None
+        self.last_fx = self.last_fx_status = None
 
     # ------------------------------------------------------------------ staging
     def resampler(self, rate):
@@ -274,13 +331,14 @@ class SoundscapeClips(object):
         return self.flat[int(self.src_off[src]):int(self.src_off[src + 1])]
 
     # ------------------------------------------------------------------ plans
-    def draw(self, B, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None, fade_seconds=0.01, background=True):
+    def draw(self, B, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None, fade_seconds=0.01, background=True,
+             pitch_shift=None, time_stretch=None):
         """the SoundscapePlan of B fresh soundscapes: draw_plan over the staged bank (module docstring)"""
         if not self.ns:
             raise ValueError('SoundscapeClips.draw: the bank is empty: add_events() first')
         level = self.level_amp if self.level == 'lufs' else self.rms
         return draw_plan(B, self.ns, level, self.by_class, self.backgrounds, self.window, self.mel.sr, n_events, snr_db, ref_db,
-                         max_event_seconds, fade_seconds, background)
+                         max_event_seconds, fade_seconds, background, pitch_shift, time_stretch)
 
     def plan(self, backgrounds, events):
         """a SoundscapePlan from hand-made records (make_plan); class names in the events' second field are looked up"""
@@ -299,9 +357,54 @@ class SoundscapeClips(object):
                                        z(B, torch.int32), z(B * chunks, torch.float32), z(B, torch.float32), z(B, torch.float32))
         return buf
 
+    def stretcher(self):
+        """the DeviceStretch of the plans' effects (n_fft = ``stretch_n_fft``, the filter of ``resample_quality``), made at first use"""
+        if self._stretch is None:
+            from .stretch import DeviceStretch
+            self._stretch = DeviceStretch(self.mel.sr, self.stretch_n_fft, self.resample_quality, device=self.dev)
+        return self._stretch
+
+    def _effect_records(self, plan):
+        """the host half of a plan's effects, None when every event is the identity: (the events with the transformed ones rewritten to
+        (src = their own row behind the bank, src_start = 0, n = m), their SedtStretchJob records, the source table extended by one row
+        per transformed event - offsets and lengths -, the samples the bank and the results take together, the workspace floats).
+        A transformed event whose record does not lie inside the bank is left as it is: sedt_soundscape raises its clip's status."""
+        from .stretch import stretch_jobs
+        ev, n_src, ns = plan.ev, len(self.ns), np.asarray(self.ns, np.int64)
+        src = np.clip(ev['src'], 0, n_src - 1)
+        inside = (ev['src'] >= 0) & (ev['src'] < n_src) & (ev['src_start'] >= 0) & (ev['n'] >= 1) & (ev['src_start'] <= ns[src]) & \
+            (ev['n'] <= ns[src] - ev['src_start'])
+        todo = np.flatnonzero(~is_identity(plan.fx) & inside)
+        if not len(todo):
+            return None
+        jobs, floats = stretch_jobs(ev['n'][todo], plan.fx['factor'][todo].astype(np.float64), plan.fx['semitones'][todo].astype(np.float64),
+                                    self.stretch_n_fft, src_offs=self.src_off[ev['src'][todo]] + ev['src_start'][todo])
+        bank = (int(self.src_off[-1]) + 3) & ~3                       # every result starts on a multiple of 4 samples behind the bank
+        jobs['dst_off'] += bank
+        out = ev.copy()
+        out['src'][todo], out['src_start'][todo], out['n'][todo] = n_src + np.arange(len(todo)), 0, jobs['m']
+        rows_off = np.concatenate([self.src_off[:-1], jobs['dst_off']]).astype(np.int64)
+        rows_len = np.concatenate([ns, jobs['m']]).astype(np.int64)
+        return out, jobs, rows_off, rows_len, int(jobs['dst_off'][-1] + jobs['m'][-1]), floats
+
+    def _effect_buffer(self, samples):
+        """the f32 device buffer that holds the bank and, behind it, the transformed sounds of one batch: the bank is copied into it
+        once (again after add_events / add_backgrounds, or when a batch needs more room than any before it)"""
+        bank = int(self.src_off[-1])
+        if self._fx_buf is None or self._fx_bank is not self.flat or self._fx_buf.numel() < samples:
+            room = samples - bank
+            self._fx_buf = torch.empty(bank + max(2 * room, 1 << 16), dtype=torch.float32, device=self.dev)
+            self._fx_buf[:bank].copy_(self.flat[:bank])
+            self._fx_bank = self.flat
+        return self._fx_buf
+
     def mix(self, plan, status=None):
         """ONE sedt_soundscape call on the current stream into this object's buffers: (wave (B, window) f32 on the device, samples per
         clip - the window - as a host list, DeviceTargets).  The records travel through a ring of pinned buffers; nothing synchronises.
+        A plan with effects (``fx``) runs sedt_stretch first, over its events that are not the identity: their results lie behind a
+        copy of the bank in a buffer of this object's, the source table is extended by one row each, and the unchanged mixing call
+        reads them as sources (``last_fx``: the jobs, the rewritten events, the buffer).  A plan without ``fx``, or with nothing but
+        identities, issues the same call on the same bytes as before.
         ``status``: an int32 [B] device tensor to raise the statuses in instead of the buffer's own (a row of a log,
         engine.train_on_recordings).  ``last_peak`` / ``last_scale`` are the clips' peaks before scaling and their scales, on the device."""
         if self.table is None:
@@ -311,16 +414,32 @@ class SoundscapeClips(object):
             raise ValueError(f'SoundscapeClips.mix: 1 .. {L.SCAPE_MAXB} clips per call')
         if self._ring is None:
             self._ring = PinnedRing(self.dev)
-        ev = plan.ev if E else np.zeros(1, EVENT)
-        raw = self._ring.upload(np.concatenate([plan.bg.view(np.uint8), ev.view(np.uint8), plan.ev_off.view(np.uint8)]))
-        n_bg, n_ev = BACKGROUND.itemsize * B, EVENT.itemsize * ev.shape[0]
-        d_bg, d_ev, d_off = raw[:n_bg], raw[n_bg:n_bg + n_ev], raw[n_bg + n_ev:n_bg + n_ev + 4 * (B + 1)]
         wave, blob, own, part, peak, scale = self.buffers(B)
         status = own if status is None else status
         if status.shape != (B,) or status.dtype != torch.int32 or not status.is_contiguous() or status.device != wave.device:
             raise ValueError('SoundscapeClips.mix: status is a contiguous int32 [B] tensor on the device')
-        L.check(L.load().sedt_soundscape(L.p(self.flat), int(self.src_off[-1]), L.p(self.table['off']), L.p(self.table['len']),
-                                         len(self.ns), L.p(d_bg), L.p(d_ev), L.p(d_off), B, self.window, self.mel.sr, self.max_targets,
+        ev = plan.ev if E else np.zeros(1, EVENT)
+        fx = self._effect_records(plan) if plan.fx is not None and E else None
+        self.last_fx = None
+        if fx is None:                                               # no effects: the call and the bytes of a plan without ``fx``
+            flat, flat_len, n_src, tail = self.flat, int(self.src_off[-1]), len(self.ns), []
+        else:
+            ev, jobs, rows_off, rows_len, flat_len, floats = fx
+            flat, n_src = self._effect_buffer(flat_len), len(self.ns) + len(jobs)
+            tail = [np.zeros(-(BACKGROUND.itemsize * B + EVENT.itemsize * ev.shape[0] + 4 * (B + 1)) % 8, np.uint8),
+                    rows_off.view(np.uint8), rows_len.view(np.uint8), jobs.view(np.uint8)]
+        raw = self._ring.upload(np.concatenate([plan.bg.view(np.uint8), ev.view(np.uint8), plan.ev_off.view(np.uint8)] + tail))
+        n_bg, n_ev = BACKGROUND.itemsize * B, EVENT.itemsize * ev.shape[0]
+        d_bg, d_ev, d_off = raw[:n_bg], raw[n_bg:n_bg + n_ev], raw[n_bg + n_ev:n_bg + n_ev + 4 * (B + 1)]
+        t_off, t_len = self.table['off'], self.table['len']
+        if fx is not None:                                           # the stage first: its results are the sources of the rows behind the bank
+            o = n_bg + n_ev + 4 * (B + 1) + tail[0].size
+            t_off, t_len, d_jobs = raw[o:o + 8 * n_src], raw[o + 8 * n_src:o + 16 * n_src], raw[o + 16 * n_src:]
+            st = self.stretcher()
+            self.last_fx_status = st.launch(flat, jobs, flat, st.workspace(floats), jobs_dev=d_jobs)
+            self.last_fx = dict(jobs=jobs, events=ev, flat=flat, workspace=st.workspace(floats))
+        L.check(L.load().sedt_soundscape(L.p(flat), flat_len, L.p(t_off), L.p(t_len), n_src, L.p(d_bg), L.p(d_ev), L.p(d_off), B,
+                                         self.window, self.mel.sr, self.max_targets,
                                          self.min_event_seconds, int(self.collapse), self.peak_limit, L.p(wave), L.p(part), L.p(peak),
                                          L.p(scale), L.p(blob), L.p(status), L.stream_ptr()), 'soundscape')
         self.last_peak, self.last_scale = peak, scale
