@@ -55,6 +55,8 @@
  *                                                                             of the sources of a bank, and gains applied in place
  *   sedt_stretch / sedt_stretch_workspace / sedt_stretch_ok                   no counterpart: per-event time stretch and pitch shift
  *                                                                             (phase vocoder, then resampling at a real ratio)
+ *   sedt_reverb / sedt_reverb_spectra / sedt_reverb_workspace / sedt_reverb_ok no counterpart: per-event reverberation with room
+ *   / sedt_reverb_bed                                                         impulse responses (partitioned FFT convolution)
  *   sedt_mixup_plan                                                           mixup_data's label half  utilities/mixup.py:30-127
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
@@ -1359,6 +1361,78 @@ int64_t sedt_stretch_workspace(const SedtStretchJob* jobs_host, int n_jobs, int 
 int sedt_stretch(const float* flat, int64_t flat_len, const SedtStretchJob* jobs_host, const SedtStretchJob* jobs_dev, int n_jobs,
                  float* dst, int64_t dst_len, void* workspace, int64_t workspace_bytes, const float* window, const float* twiddle,
                  const float* wtab, int zero_crossings, int n_fft, int32_t* status, void* stream);
+/* sedt_reverb (no counterpart in the reference, whose corpora were generated offline; DESIGN.md section 4, "Reverberation on the
+ * device"; tests/reverb_ref.py restates it in float64): n_jobs excerpts of a bank, each convolved with a room impulse response (RIR)
+ * of a staged RIR bank - uniformly partitioned overlap-save convolution.  N = n_fft, Bs = N / 2, K = N / 2 + 1.
+ * The RIR bank.  rir_tab int64 [3][n_rirs]: row 0 the taps L_r (1 <= L_r <= SEDT_REVERB_MAXPART Bs), row 1 the response's first
+ *   partition - the responses' P_r = ceil(L_r / Bs) partitions lie behind one another, n_parts in all -, row 2 its first tap in
+ *   `taps` (read by sedt_reverb_spectra only).  sedt_reverb_spectra writes h_re / h_im f32 [n_parts][K] in ONE launch: H[r][p] = the
+ *   N-point real FFT of taps [p Bs, (p + 1) Bs) of response r followed by Bs zeros (the last partition zero-padded).
+ * Job e: x[i] = flat[src_off + i] w(i), 0 <= i < n, w the ramp of sedt_soundscape over n samples with the job's `fade` (one f32
+ *   product; fade 0: x itself) - the fades belong to the dry sound, not to its tail; wet = dst[dst_off .. dst_off + n + L - 1), L the
+ *   taps of response `rir`.
+ *   Input block j, 0 <= j < nb = ceil(n / Bs) + 1, holds x[(j - 1) Bs .. (j + 1) Bs), zero outside [0, n); X[j] = its N-point real
+ *     FFT, bins 0 .. N/2, f32.
+ *   Output block j, 0 <= j < ceil((n + L - 1) / Bs): Y = the sum over p = 0 .. P - 1, ascending, of X[j - p] H[r][p] (complex f32
+ *     products and sums; X[i] = 0 for i outside 0 .. nb - 1); the inverse real FFT of Y (the imaginary parts of bins 0 and N/2
+ *     dropped); its LAST Bs samples are wet[j Bs .. (j + 1) Bs), clipped to n + L - 1.
+ * twiddle f32 [2][N/2 + 1] is sedt_mel_spectrogram's table.
+ * The records and the RIR table exist twice: jobs_host / rir_tab_host are read by the entry point (refusals, grid sizes), jobs_dev /
+ * rir_tab_dev - the same bytes in DEVICE memory - by the kernels, which check every record again before they touch memory.
+ * Workspace: the caller's; job e owns floats [ws_off, ws_off + F_e), F_e = 2 nb K rounded up to a multiple of 4, laid out
+ *   X re [nb][K] | X im [nb][K].  ws_off is a multiple of 4 and the regions follow one another in job order.  sedt_reverb_workspace
+ *   returns the bytes a job list needs, -1 with a message for a list the entry point would refuse.
+ * status int32 [n_jobs]: 0; 2 the DEVICE record does not lie inside the bank, the destination, the workspace or the RIR table, or is
+ *   outside the envelope - nothing is read or written for it.
+ * group: the output blocks a workgroup of the second launch keeps in registers (1, 2, 4, 8; 0: the library's choice).  The bits do
+ *   not depend on it.
+ * Two launches behind one another on `stream` (the blocks' spectra; products, inverse and store), no atomics - the same call gives the
+ * same bits; no allocation, no synchronisation; capturable.
+ * Envelope (sedt_reverb_ok): n_fft 512, 1024 or 2048; 1 <= n <= 2^26; 0 <= fade <= 2^26; 1 <= L <= SEDT_REVERB_MAXPART n_fft / 2 - at
+ *   n_fft 2048 that is 180224 taps: a response of 4 s at 44.1 kHz (176400) fits.  A job or a response outside it, regions or
+ *   partitions out of order, a workspace smaller than the list needs, a negative count or length, more than 65535 jobs or responses
+ *   or a null pointer: non-zero with a message before anything is launched.  n_jobs == 0 returns 0 and launches nothing. */
+#define SEDT_REVERB_MAXPART 176
+typedef struct {
+  int64_t src_off, n;               /* the dry sound: flat[src_off .. src_off + n) */
+  int64_t dst_off;                  /* the wet sound: dst[dst_off .. dst_off + n + L - 1) */
+  int32_t rir, fade;                /* the response's index; samples of the linear ramp at both ends of the dry sound */
+  int64_t ws_off;                   /* the job's first float in the workspace */
+} SedtReverbJob;                    /* 40 bytes; sedt_sizeof index 16 */
+int sedt_reverb_ok(int n_fft, int64_t n, int64_t taps, int fade);
+int64_t sedt_reverb_workspace(const SedtReverbJob* jobs_host, int n_jobs, int n_fft);
+int sedt_reverb_spectra(const float* taps, int64_t taps_len, const int64_t* rir_tab_host, const int64_t* rir_tab_dev, int n_rirs,
+                        float* h_re, float* h_im, int64_t n_parts, const float* twiddle, int n_fft, void* stream);
+int sedt_reverb(const float* flat, int64_t flat_len, const SedtReverbJob* jobs_host, const SedtReverbJob* jobs_dev, int n_jobs,
+                float* dst, int64_t dst_len, void* workspace, int64_t workspace_bytes, const float* h_re, const float* h_im,
+                int64_t n_parts, const int64_t* rir_tab_host, const int64_t* rir_tab_dev, int n_rirs, const float* twiddle, int n_fft,
+                int group, int32_t* status, void* stream);
+/* sedt_reverb_bed: the tails of the wet events of n_beds clips laid over the clips' backgrounds, one row of `window` samples per clip
+ * (utilities/soundscape.py hands the row to sedt_soundscape as the clip's background).  float32 with every operation rounded on its
+ * own (no contraction).  For sample t of bed c (DEVICE records; the bank as for sedt_bank_stats):
+ *   acc = gain * src[(start + t) mod len] of source `src`; src == -1: acc = 0;
+ *   for every tail k in tail_lo <= k < tail_hi, ascending, with head <= t - onset < total: acc = acc + (gain_k * flat[wet_off + t - onset]);
+ *   dst[dst_off + t] = acc.
+ * A background or a tail that does not lie inside flat contributes nothing; a bed whose row does not lie inside dst is not written.
+ * One launch, one thread per sample; no atomics, no allocation, no synchronisation; capturable.  dst may be flat itself as long as
+ * the rows do not overlap what is read. */
+typedef struct {
+  int64_t wet_off;                  /* the wet sound's first sample in flat */
+  int64_t onset;                    /* its sample 0 lies at sample `onset` of the clip */
+  int64_t head, total;              /* samples head .. total - 1 of it are the tail */
+  float gain;
+  int32_t pad;
+} SedtReverbTail;                   /* 40 bytes; sedt_sizeof index 17 */
+typedef struct {
+  int32_t src, tail_lo;             /* the background's source index, -1: none; the clip's first tail */
+  int64_t start;                    /* the background's sample under sample 0 of the clip */
+  float gain;
+  int32_t tail_hi;                  /* one past the clip's last tail */
+  int64_t dst_off;                  /* the bed row: dst[dst_off .. dst_off + window) */
+} SedtReverbBed;                    /* 32 bytes; sedt_sizeof index 18 */
+int sedt_reverb_bed(const float* flat, int64_t flat_len, const int64_t* src_off, const int64_t* src_len, int n_src,
+                    const SedtReverbBed* beds, int n_beds, const SedtReverbTail* tails, int n_tails, int64_t window, float* dst,
+                    int64_t dst_len, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

@@ -22,6 +22,8 @@ SCAPE_MAXEV = 63       # sedt_soundscape: events per clip (SEDT_SCAPE_MAXEV)
 SCAPE_CHUNK = 2048     # sedt_soundscape: samples per mixing workgroup (SEDT_SCAPE_CHUNK)
 STRETCH_MAXJOBS = 65535   # sedt_stretch: jobs per call
 STRETCH_TABLE_RES = 512   # sedt_stretch: table points per zero crossing of the resampling filter
+REVERB_MAXJOBS = 65535    # sedt_reverb: jobs per call, responses per bank
+REVERB_MAXPART = 176      # sedt_reverb: partitions of n_fft / 2 taps per response (SEDT_REVERB_MAXPART)
 GEMM_X3 = False       # runtime.set_compute_dtype('bf16x3'): the f32 mode's contractions go through the BF16X3 code
 
 
@@ -231,6 +233,11 @@ SIGNATURES = {
     'sedt_stretch_ok': (_i, [_i, _i64, _i64, _i64, _d, _d, _i, _i]),
     'sedt_stretch_workspace': (_i64, [_vp, _i, _i]),
     'sedt_stretch': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'sedt_reverb_ok': (_i, [_i, _i64, _i64, _i]),
+    'sedt_reverb_workspace': (_i64, [_vp, _i, _i]),
+    'sedt_reverb_spectra': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _vp]),
+    'sedt_reverb': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    'sedt_reverb_bed': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i64, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_mixup_plan': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

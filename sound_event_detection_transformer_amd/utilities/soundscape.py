@@ -29,6 +29,16 @@ the reference is the source's BS.1770 loudness L as Scaper's is (utilities/loudn
 staged): 10^(L / 20) stands where the RMS stands, so g = 10^((ref_db + snr - L) / 20), and ref_db and snr are LUFS values.  Nothing
 else changes: the same draws in the same order, the same mixing.  fade = round(fade_seconds * sr) samples of linear ramp at both ends
 of an event.
+    With ``reverb=True`` or ``reverb=prob`` (0 < prob <= 1) and room impulse responses staged (``add_rirs``; utilities/reverb.py) the plan
+    gains ``rir``, int32 [E], -1: dry.  Per clip, right after the background draw: room = randint(n_rooms).  Per event, right after the
+    effect draws and before src_start: with a probability, uniform() < prob decides whether the event is wet (``True`` draws nothing
+    here); a wet event then draws rir = the room's responses[randint(count)], a dry one draws nothing more.  n, m and the onset are
+    drawn as before: the tail is NOT made to fit the window.  With reverb=None nothing new is drawn.  ``mix`` runs sedt_reverb behind
+    the stretch stage, over the wet events: a wet event's first m samples (the head) go to the mixing call as the event - same onset,
+    class and gain, fade 0, the stage applied the fades to the dry sound - so the annotations stay those of the dry event; its last
+    L - 1 samples (the tail) are laid, with the event's gain, over the clip's background in a bed row of ``window`` samples
+    (sedt_reverb_bed) that becomes the clip's background record (row, 0, 1.0).  The wet level is not measured again, backgrounds stay
+    dry, and the tail past the window's end is cut.
 
 ``draw_plan``, ``make_plan``, ``gains`` and the record dtypes are the host half and need no GPU."""
 import math
@@ -54,18 +64,22 @@ class SoundscapePlan(object):
     """the records of B soundscapes as sedt_soundscape reads them: ``bg`` BACKGROUND [B] (src -1: no background), ``ev`` EVENT [E],
     ``ev_off`` int32 [B + 1] - clip b's events are ev[ev_off[b]:ev_off[b + 1]], mixed in that order.  ``fx``: None (no effects) or FX [E],
     the pitch shift and duration factor of every event; an event's ``n`` is then the length of its EXCERPT, and it occupies
-    floor(n factor + 0.5) samples of the clip from ``onset`` on"""
+    floor(n factor + 0.5) samples of the clip from ``onset`` on.  ``rir``: None (all dry) or int32 [E], the room impulse response every
+    event is convolved with, -1: dry"""
 
-    def __init__(self, bg, ev, ev_off, fx=None):
+    def __init__(self, bg, ev, ev_off, fx=None, rir=None):
         self.bg = np.ascontiguousarray(bg, BACKGROUND)
         self.ev = np.ascontiguousarray(ev, EVENT)
         self.ev_off = np.ascontiguousarray(ev_off, np.int32)
         self.fx = None if fx is None else np.ascontiguousarray(fx, FX)
+        self.rir = None if rir is None else np.ascontiguousarray(rir, np.int32)
         B = self.bg.shape[0]
         if self.bg.shape != (B,) or self.ev_off.shape != (B + 1,) or self.ev.ndim != 1:
             raise ValueError('SoundscapePlan: bg [B], ev [E], ev_off [B + 1]')
         if self.fx is not None and self.fx.shape != self.ev.shape:
             raise ValueError('SoundscapePlan: fx [E], one (semitones, factor) per event')
+        if self.rir is not None and self.rir.shape != self.ev.shape:
+            raise ValueError('SoundscapePlan: rir [E], one response index per event (-1: dry)')
         if self.ev_off[0] != 0 or self.ev_off[-1] != self.ev.shape[0] or bool((np.diff(self.ev_off) < 0).any()):
             raise ValueError('SoundscapePlan: ev_off is not the exclusive scan of the clips\' event counts')
         if B and int(np.diff(self.ev_off).max()) > L.SCAPE_MAXEV:
@@ -106,11 +120,12 @@ def check_bank_loudness(what, lufs, classes):
                              'sound needs a loudness to be placed at an SNR')
 
 
-def make_plan(backgrounds, events):
+def make_plan(backgrounds, events, rirs=None):
     """a SoundscapePlan from hand-made records: ``backgrounds`` one entry per clip, None or (src, start, gain); ``events`` one list per
     clip of (src, cls, src_start, n, onset, gain, fade) or, with effects, (src, cls, src_start, n, onset, gain, fade, semitones,
     factor) - the plan has ``fx`` as soon as one event has the two trailing fields, the others are the identity.  Nothing but the
-    shape and the event count per clip is checked here: a record outside the bank raises the clip's status on the device."""
+    shape and the event count per clip is checked here: a record outside the bank raises the clip's status on the device.
+    ``rirs``: None, or one list per clip with one response index per event (-1: dry) - the plan's ``rir``."""
     if len(backgrounds) != len(events):
         raise ValueError('make_plan: one background entry and one event list per clip')
     bg = np.zeros(len(backgrounds), BACKGROUND)
@@ -126,7 +141,12 @@ def make_plan(backgrounds, events):
     off = np.concatenate([[0], np.cumsum([len(c) for c in events])]).astype(np.int64)
     if len(events) and int(np.diff(off).max()) > L.SCAPE_MAXEV:
         raise ValueError(f'make_plan: a clip holds {int(np.diff(off).max())} events, sedt_soundscape takes {L.SCAPE_MAXEV}')
-    return SoundscapePlan(bg, ev, off.astype(np.int32), fx)
+    rir = None
+    if rirs is not None:
+        if len(rirs) != len(events) or any(len(r) != len(c) for r, c in zip(rirs, events)):
+            raise ValueError('make_plan: rirs holds one list per clip, one response index per event')
+        rir = np.asarray([int(i) for r in rirs for i in r], np.int32)
+    return SoundscapePlan(bg, ev, off.astype(np.int32), fx, rir)
 
 
 def is_identity(fx):
@@ -145,11 +165,21 @@ def excerpt_for(limit, factor):
 
 
 def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None,
-              fade_seconds=0.01, background=True, pitch_shift=None, time_stretch=None):
+              fade_seconds=0.01, background=True, pitch_shift=None, time_stretch=None, reverb=None, rooms=None):
     """the plan of B soundscapes (module docstring: the order np.random is consumed in).  lens / rms: samples and float64 level per
     source as an amplitude (the RMS, or 10^(L / 20) under level='lufs'); by_class: per class the source indices of its sounds;
     backgrounds: the source indices of the background recordings; pitch_shift / time_stretch: None or the (lo, hi) range an event's
-    shift in semitones / duration factor is drawn from - with both None nothing new is drawn and the plan has no ``fx``"""
+    shift in semitones / duration factor is drawn from - with both None nothing new is drawn and the plan has no ``fx``; reverb: None,
+    True (every event wet) or the probability in (0, 1] that an event is wet; rooms: per room the indices of its responses"""
+    wet_prob = None
+    if reverb is not None and reverb is not False:
+        if not rooms or any(not len(r) for r in rooms):
+            raise ValueError('draw: reverb asked for, no room impulse response is staged: add_rirs() first')
+        if reverb is not True:
+            wet_prob = float(reverb)
+            if not 0.0 < wet_prob <= 1.0:                    # (NaN fails)
+                raise ValueError(f'draw: reverb {reverb!r} is neither True nor a probability in (0, 1]')
+    wet_draws = reverb is not None and reverb is not False
     effects = pitch_shift is not None or time_stretch is not None
     if effects:
         from .stretch import check_effect
@@ -176,11 +206,13 @@ def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), 
     fade = int(round(float(fade_seconds) * sr))
     bg = np.zeros(int(B), BACKGROUND)
     bg['src'] = -1
-    ev, fx, off = [], [], [0]
+    ev, fx, rir, off = [], [], [], [0]
     for b in range(int(B)):
         if background:
             s = int(backgrounds[np.random.randint(len(backgrounds))])
             bg[b]['src'], bg[b]['start'], bg[b]['gain'] = s, np.random.randint(int(lens[s])), gains(ref_db, 0.0, rms[s])
+        if wet_draws:
+            room = rooms[np.random.randint(len(rooms))]
         for _ in range(np.random.randint(lo, hi + 1)):
             c = classes[np.random.randint(len(classes))]
             s = int(by_class[c][np.random.randint(len(by_class[c]))])
@@ -196,12 +228,15 @@ def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), 
                     raise ValueError(f'draw: no excerpt stretched by {float(f)} fits {min(cap, window)} samples')
                 m = int(math.floor(n * float(f) + 0.5))
                 fx.append((p, f))
+            if wet_draws:
+                wet = True if wet_prob is None else bool(np.random.uniform() < wet_prob)
+                rir.append(int(room[np.random.randint(len(room))]) if wet else -1)
             src_start = np.random.randint(int(lens[s]) - n + 1)
             onset = np.random.randint(window - m + 1)
             ev.append((s, c, src_start, n, onset, gains(ref_db, snr, rms[s]), fade))
         off.append(len(ev))
     return SoundscapePlan(bg, np.array(ev, EVENT) if ev else np.zeros(0, EVENT), np.asarray(off, np.int32),
-                          np.array(fx, FX).reshape(-1) if effects else None)
+                          np.array(fx, FX).reshape(-1) if effects else None, np.asarray(rir, np.int32) if wet_draws else None)
 
 
 class SoundscapeClips(object):
@@ -211,12 +246,13 @@ class SoundscapeClips(object):
     overlap or touch, as data_utils/collapse_event.py does for the reference's corpora; peak_limit: a clip whose peak exceeds it is
     scaled down to it; level: 'rms' - ref_db and snr_db refer to the sources' RMS - or 'lufs' - to their BS.1770 loudness, measured on
     the device at staging (``lufs``, ``level_amp`` = 10^(lufs / 20) per source); stretch_n_fft: the frame length of the effects' phase
-    vocoder (512, 1024 or 2048; the resampling filter is ``resample_quality``'s).  See the module docstring."""
+    vocoder (512, 1024 or 2048; the resampling filter is ``resample_quality``'s); reverb_n_fft: the frame length of the reverberation's
+    partitioned convolution (512, 1024 or 2048).  See the module docstring."""
 
     STATUS_REASONS = STATUS_REASONS
 
     def __init__(self, mel, labels, window_seconds=10.0, max_targets=32, min_event_seconds=0.0, collapse=True, peak_limit=1.0,
-                 device='cuda', resample_quality='kaiser_best', level='rms', stretch_n_fft=2048):
+                 device='cuda', resample_quality='kaiser_best', level='rms', stretch_n_fft=2048, reverb_n_fft=2048):
         self.mel, self.labels = mel, list(labels)
         self.window_seconds = float(window_seconds)
         self.window = int(round(self.window_seconds * mel.sr))
@@ -244,7 +280,8 @@ class SoundscapeClips(object):
         self.last_peak = self.last_scale = None
         self._ring, self._buf, self._amp, self._keep = None, {}, {}, []
         self.stretch_n_fft, self._stretch, self._fx_buf, self._fx_bank = int(stretch_n_fft), None, None, None
-        self.last_fx = self.last_fx_status = None
+        self.last_fx = self.last_fx_status = self.last_rv_status = None
+        self.reverb_n_fft, self._reverb, self.rooms, self._room_ids = int(reverb_n_fft), None, [], []
 
     # ------------------------------------------------------------------ staging
     def resampler(self, rate):
@@ -323,6 +360,31 @@ class SoundscapeClips(object):
         waves = list(waves)
         return self._add('add_backgrounds', waves, [-1] * len(waves), sample_rates)
 
+    def reverberator(self):
+        """the DeviceReverb of the plans' wet events (n_fft = ``reverb_n_fft``), made at first use"""
+        if self._reverb is None:
+            from .reverb import DeviceReverb
+            self._reverb = DeviceReverb(self.mel.sr, self.reverb_n_fft, device=self.dev, resample_quality=self.resample_quality)
+        return self._reverb
+
+    def add_rirs(self, rirs, rooms=None, sample_rates=None, normalize='energy'):
+        """stage room impulse responses (DeviceReverb.add_rirs: 1-D float32 / int16 at mel.sr or, with ``sample_rates``, resampled on the
+        device; normalize='energy' scales each to sum h^2 = 1).  rooms: one room id per response - a clip draws ONE room and its wet
+        events draw among that room's responses; the default puts every response into one room.  Returns self."""
+        rirs = list(rirs)
+        ids = [0] * len(rirs) if rooms is None else list(rooms)
+        if len(ids) != len(rirs):
+            raise ValueError('SoundscapeClips.add_rirs: one room id per response')
+        rv = self.reverberator()
+        first = len(rv)
+        rv.add_rirs(rirs, sample_rates=sample_rates, normalize=normalize)
+        for i, room in enumerate(ids):
+            if room not in self._room_ids:
+                self._room_ids.append(room)
+                self.rooms.append([])
+            self.rooms[self._room_ids.index(room)].append(first + i)
+        return self
+
     def __len__(self):
         return len(self.ns)
 
@@ -332,18 +394,18 @@ class SoundscapeClips(object):
 
     # ------------------------------------------------------------------ plans
     def draw(self, B, n_events=(1, 9), snr_db=(6.0, 30.0), ref_db=-30.0, max_event_seconds=None, fade_seconds=0.01, background=True,
-             pitch_shift=None, time_stretch=None):
+             pitch_shift=None, time_stretch=None, reverb=None):
         """the SoundscapePlan of B fresh soundscapes: draw_plan over the staged bank (module docstring)"""
         if not self.ns:
             raise ValueError('SoundscapeClips.draw: the bank is empty: add_events() first')
         level = self.level_amp if self.level == 'lufs' else self.rms
         return draw_plan(B, self.ns, level, self.by_class, self.backgrounds, self.window, self.mel.sr, n_events, snr_db, ref_db,
-                         max_event_seconds, fade_seconds, background, pitch_shift, time_stretch)
+                         max_event_seconds, fade_seconds, background, pitch_shift, time_stretch, reverb, self.rooms)
 
-    def plan(self, backgrounds, events):
+    def plan(self, backgrounds, events, rirs=None):
         """a SoundscapePlan from hand-made records (make_plan); class names in the events' second field are looked up"""
         events = [[(e[0], self._class_index(e[1]) if isinstance(e[1], str) else e[1]) + tuple(e[2:]) for e in clip] for clip in events]
-        return make_plan(backgrounds, events)
+        return make_plan(backgrounds, events, rirs)
 
     # ------------------------------------------------------------------ batches
     def buffers(self, B):
@@ -387,6 +449,54 @@ class SoundscapeClips(object):
         rows_len = np.concatenate([ns, jobs['m']]).astype(np.int64)
         return out, jobs, rows_off, rows_len, int(jobs['dst_off'][-1] + jobs['m'][-1]), floats
 
+    def _reverb_records(self, plan, ev, rows_off, rows_len, end):
+        """the host half of a plan's reverberation, None when no event is wet.  ``ev``: the events after the stretch stage's rewrite;
+        ``rows_off`` / ``rows_len``: the source table so far; ``end``: the samples the bank and the stretched rows take.  Returns a dict:
+        ev - the wet events rewritten to their heads (src = the wet row, src_start 0, the same n, fade 0); bg - the clips that hold a
+        wet event rewritten to (bed row, 0, 1.0); jobs (SedtReverbJob), tails, beds; the table extended by the wet rows and the bed
+        rows; the samples in all; the workspace floats.  An event whose record does not lie inside the bank, and every event of a clip
+        whose background record does not, is left as it is: sedt_soundscape raises the clip's status."""
+        from .reverb import BED, TAIL, reverb_jobs
+        rv, B, n_src = self._reverb, len(plan), len(self.ns)
+        if rv is None or not len(rv):
+            raise ValueError('SoundscapeClips.mix: the plan has wet events, no room impulse response is staged: add_rirs() first')
+        rir = plan.rir
+        if int(rir.max()) >= len(rv):
+            raise ValueError(f'SoundscapeClips.mix: the plan names response {int(rir.max())}, {len(rv)} are staged')
+        n_rows, ns = len(rows_len), np.asarray(self.ns, np.int64)
+        src = np.clip(ev['src'], 0, n_rows - 1)
+        inside = (ev['src'] >= 0) & (ev['src'] < n_rows) & (ev['src_start'] >= 0) & (ev['n'] >= 1) & (ev['onset'] >= 0) & \
+            (ev['src_start'] <= rows_len[src]) & (ev['n'] <= rows_len[src] - ev['src_start'])
+        g = plan.bg
+        gs = np.clip(g['src'], 0, n_src - 1)
+        bg_ok = (g['src'] == -1) | ((g['src'] >= 0) & (g['src'] < n_src) & (g['start'] >= 0) & (g['start'] < ns[gs]))
+        clip_of = np.repeat(np.arange(B), np.diff(plan.ev_off))
+        wet = np.flatnonzero((rir >= 0) & inside & bg_ok[clip_of])
+        if not len(wet):
+            return None
+        jobs, floats = reverb_jobs(ev['n'][wet], rir[wet], rv.rir_lens, self.reverb_n_fft,
+                                   src_offs=rows_off[ev['src'][wet]] + ev['src_start'][wet], fades=np.maximum(ev['fade'][wet], 0))
+        jobs['dst_off'] += (int(end) + 3) & ~3                       # every wet row starts on a multiple of 4 samples behind what is there
+        totals = (jobs['n'] + np.asarray(rv.rir_lens, np.int64)[jobs['rir']] - 1).astype(np.int64)
+        out = ev.copy()
+        out['src'][wet], out['src_start'][wet], out['fade'][wet] = n_rows + np.arange(len(wet)), 0, 0
+        clips = np.unique(clip_of[wet])
+        row = (self.window + 3) & ~3
+        bed_off = ((int(jobs['dst_off'][-1] + totals[-1]) + 3) & ~3) + row * np.arange(len(clips), dtype=np.int64)
+        tails = np.zeros(len(wet), TAIL)
+        tails['wet_off'], tails['onset'], tails['head'], tails['total'], tails['gain'] = jobs['dst_off'], ev['onset'][wet], ev['n'][wet], \
+            totals, ev['gain'][wet]
+        beds = np.zeros(len(clips), BED)
+        beds['src'], beds['start'], beds['gain'] = g['src'][clips], g['start'][clips], g['gain'][clips]
+        beds['tail_lo'], beds['tail_hi'] = np.searchsorted(clip_of[wet], clips, 'left'), np.searchsorted(clip_of[wet], clips, 'right')
+        beds['dst_off'] = bed_off
+        bg = g.copy()
+        bg['src'][clips], bg['start'][clips], bg['gain'][clips] = n_rows + len(wet) + np.arange(len(clips)), 0, np.float32(1.0)
+        return dict(ev=out, bg=bg, jobs=jobs, tails=tails, beds=beds, wet=wet, clips=clips,
+                    rows_off=np.concatenate([rows_off, jobs['dst_off'], bed_off]).astype(np.int64),
+                    rows_len=np.concatenate([rows_len, totals, np.full(len(clips), self.window)]).astype(np.int64),
+                    samples=int(bed_off[-1]) + self.window, floats=floats)
+
     def _effect_buffer(self, samples):
         """the f32 device buffer that holds the bank and, behind it, the transformed sounds of one batch: the bank is copied into it
         once (again after add_events / add_backgrounds, or when a batch needs more room than any before it)"""
@@ -405,6 +515,10 @@ class SoundscapeClips(object):
         copy of the bank in a buffer of this object's, the source table is extended by one row each, and the unchanged mixing call
         reads them as sources (``last_fx``: the jobs, the rewritten events, the buffer).  A plan without ``fx``, or with nothing but
         identities, issues the same call on the same bytes as before.
+        A plan with wet events (``rir`` >= 0) then runs sedt_reverb over them - a wet event's dry input is its stretched row, or its bank
+        excerpt - and sedt_reverb_bed over the clips that hold one (module docstring); the table grows by the wet rows and the bed rows,
+        every record travels in the same pinned upload, and ``last_fx`` also reports the reverb jobs, tails and beds
+        (``last_rv_status``: the stage's statuses).  A plan without ``rir``, or with nothing but -1, issues the calls of before.
         ``status``: an int32 [B] device tensor to raise the statuses in instead of the buffer's own (a row of a log,
         engine.train_on_recordings).  ``last_peak`` / ``last_scale`` are the clips' peaks before scaling and their scales, on the device."""
         if self.table is None:
@@ -420,24 +534,50 @@ class SoundscapeClips(object):
             raise ValueError('SoundscapeClips.mix: status is a contiguous int32 [B] tensor on the device')
         ev = plan.ev if E else np.zeros(1, EVENT)
         fx = self._effect_records(plan) if plan.fx is not None and E else None
+        rvb = None
+        if plan.rir is not None and E and bool((plan.rir >= 0).any()):
+            rvb = self._reverb_records(plan, *((plan.ev, self.src_off[:-1], np.asarray(self.ns, np.int64), int(self.src_off[-1]))
+                                               if fx is None else (fx[0], fx[2], fx[3], fx[4])))
         self.last_fx = None
-        if fx is None:                                               # no effects: the call and the bytes of a plan without ``fx``
+        bg = plan.bg
+        if fx is None and rvb is None:                               # no effects: the call and the bytes of a plan without ``fx`` / ``rir``
             flat, flat_len, n_src, tail = self.flat, int(self.src_off[-1]), len(self.ns), []
         else:
-            ev, jobs, rows_off, rows_len, flat_len, floats = fx
-            flat, n_src = self._effect_buffer(flat_len), len(self.ns) + len(jobs)
+            from .stretch import JOB as STRETCH_JOB
+            jobs, floats = (np.zeros(0, STRETCH_JOB), 0) if fx is None else (fx[1], fx[5])
+            if fx is not None:
+                ev, rows_off, rows_len, flat_len = fx[0], fx[2], fx[3], fx[4]
+            if rvb is not None:
+                ev, bg, rows_off, rows_len, flat_len = rvb['ev'], rvb['bg'], rvb['rows_off'], rvb['rows_len'], rvb['samples']
+            flat, n_src = self._effect_buffer(flat_len), len(rows_len)
             tail = [np.zeros(-(BACKGROUND.itemsize * B + EVENT.itemsize * ev.shape[0] + 4 * (B + 1)) % 8, np.uint8),
                     rows_off.view(np.uint8), rows_len.view(np.uint8), jobs.view(np.uint8)]
-        raw = self._ring.upload(np.concatenate([plan.bg.view(np.uint8), ev.view(np.uint8), plan.ev_off.view(np.uint8)] + tail))
+            if rvb is not None:
+                tail += [rvb['jobs'].view(np.uint8), rvb['tails'].view(np.uint8), rvb['beds'].view(np.uint8)]
+        raw = self._ring.upload(np.concatenate([bg.view(np.uint8), ev.view(np.uint8), plan.ev_off.view(np.uint8)] + tail))
         n_bg, n_ev = BACKGROUND.itemsize * B, EVENT.itemsize * ev.shape[0]
         d_bg, d_ev, d_off = raw[:n_bg], raw[n_bg:n_bg + n_ev], raw[n_bg + n_ev:n_bg + n_ev + 4 * (B + 1)]
         t_off, t_len = self.table['off'], self.table['len']
-        if fx is not None:                                           # the stage first: its results are the sources of the rows behind the bank
+        if tail:                                                     # the stages first: their results are the sources of the rows behind the bank
             o = n_bg + n_ev + 4 * (B + 1) + tail[0].size
-            t_off, t_len, d_jobs = raw[o:o + 8 * n_src], raw[o + 8 * n_src:o + 16 * n_src], raw[o + 16 * n_src:]
-            st = self.stretcher()
-            self.last_fx_status = st.launch(flat, jobs, flat, st.workspace(floats), jobs_dev=d_jobs)
-            self.last_fx = dict(jobs=jobs, events=ev, flat=flat, workspace=st.workspace(floats))
+            t_off, t_len = raw[o:o + 8 * n_src], raw[o + 8 * n_src:o + 16 * n_src]
+            o += 16 * n_src
+            self.last_fx = dict(jobs=jobs, events=ev, flat=flat)
+            if len(jobs):
+                st = self.stretcher()
+                self.last_fx_status = st.launch(flat, jobs, flat, st.workspace(floats), jobs_dev=raw[o:o + jobs.nbytes])
+                self.last_fx['workspace'] = st.workspace(floats)
+            o += jobs.nbytes
+            if rvb is not None:
+                rj, tails, beds = rvb['jobs'], rvb['tails'], rvb['beds']
+                rv = self._reverb
+                self.last_rv_status = rv.launch(flat, rj, flat, rv.workspace(rvb['floats']), jobs_dev=raw[o:o + rj.nbytes])
+                d_tails = raw[o + rj.nbytes:o + rj.nbytes + tails.nbytes]
+                d_beds = raw[o + rj.nbytes + tails.nbytes:o + rj.nbytes + tails.nbytes + beds.nbytes]
+                L.check(L.load().sedt_reverb_bed(L.p(flat), flat_len, L.p(t_off), L.p(t_len), n_src, L.p(d_beds), len(beds), L.p(d_tails),
+                                                 len(tails), self.window, L.p(flat), flat_len, L.stream_ptr()), 'reverb_bed')
+                self.last_fx.update(reverb_jobs=rj, tails=tails, beds=beds, bg=bg, wet=rvb['wet'], clips=rvb['clips'],
+                                    rows_off=rows_off, rows_len=rows_len, reverb_workspace=rv.workspace(rvb['floats']))
         L.check(L.load().sedt_soundscape(L.p(flat), flat_len, L.p(t_off), L.p(t_len), n_src, L.p(d_bg), L.p(d_ev), L.p(d_off), B,
                                          self.window, self.mel.sr, self.max_targets,
                                          self.min_event_seconds, int(self.collapse), self.peak_limit, L.p(wave), L.p(part), L.p(peak),
