@@ -57,6 +57,9 @@
  *                                                                             (phase vocoder, then resampling at a real ratio)
  *   sedt_reverb / sedt_reverb_spectra / sedt_reverb_workspace / sedt_reverb_ok no counterpart: per-event reverberation with room
  *   / sedt_reverb_bed                                                         impulse responses (partitioned FFT convolution)
+ *   sedt_relevel / sedt_relevel_workspace                                     no counterpart: the level of every processed event (RMS or
+ *                                                                             BS.1770) measured on the device, its gain written into the
+ *                                                                             device records before they are mixed
  *   sedt_mixup_plan                                                           mixup_data's label half  utilities/mixup.py:30-127
  *   sedt_multi_sumsq / sedt_multi_adamw / sedt_adamw_clip                     clip_grad_norm_ + AdamW.step  engine.py:77-80
  *   sedt_multi_ema                                                            EMA.update            utilities/utils.py:62-67
@@ -1433,6 +1436,44 @@ typedef struct {
 int sedt_reverb_bed(const float* flat, int64_t flat_len, const int64_t* src_off, const int64_t* src_len, int n_src,
                     const SedtReverbBed* beds, int n_beds, const SedtReverbTail* tails, int n_tails, int64_t window, float* dst,
                     int64_t dst_len, void* stream);
+/* sedt_relevel (no counterpart in the reference, whose corpora were mixed offline by generators that measure every PROCESSED event
+ * before they apply its SNR; DESIGN.md section 4, "Levels measured after the effects"; tests/relevel_ref.py restates it in float64):
+ * the level of n_jobs regions of flat - an event's bank excerpt, its stretched row, its wet row - and, from it, the gain that brings
+ * the region to the job's target, written into the DEVICE records sedt_reverb_bed and sedt_soundscape read.  Nothing is read back.
+ * Job e measures flat[off .. off + n), which starts at any sample:
+ *   mode 0 (RMS):     level = (the sum of x * x) / n, every square and every addition in float64 in sedt_bank_stats' order - thread t
+ *     adds elements t, t + 256, ..., then the fixed tree over the 256 partial sums; counts = n (clamped to 2^31 - 1), 0, 0, 0.
+ *   mode 1 (BS.1770): level = zbar and counts exactly as sedt_loudness gives them for a source that is this region: coef, hop_map,
+ *     hop and z_abs are its arguments, the rounds of 256 hops with the carried state, both gates and the short-region rule are its
+ *     own (one shared device function: the same bits).  The job's hop energies go to work[ws_off .. ws_off + n / hop + 1).
+ *   g = float32(target / sqrt(level)), the division and the root in float64.  `target` is the amplitude the region shall have with
+ *     every constant folded in by the host: 10^(dB / 20) in mode 0, 10^((LUFS + 0.691) / 20) in mode 1.
+ *   level finite and > 0: status 0, g is written to ev[job.ev].gain and to tails[job.tail].gain; an index of -1 is skipped.
+ *   otherwise - a silent region, one under the absolute gate in every block, one that holds a NaN or infinite sample: status 1, and
+ *     both records keep the gain the host wrote.
+ * level float64 [n_jobs], counts int32 [n_jobs][4], status int32 [n_jobs].
+ * The records exist twice: jobs_host is read by the entry point (refusals), jobs_dev - the same bytes in DEVICE memory - by the
+ * kernel, which checks every record again before it touches memory: status 2, the DEVICE record does not lie inside flat, names a
+ * record outside ev [n_ev] / tails [n_tails], has a target that is not a finite number > 0 or a workspace region outside work -
+ * nothing but the status is written for it.  A record of ev / tails is named by at most one job of a call.
+ * Workspace: the caller's float64 work [work_len]; in mode 1 job e owns n / hop + 1 doubles from ws_off on, the regions follow one
+ *   another in job order; mode 0 needs none (work may be null, as coef and hop_map may).  sedt_relevel_workspace returns the DOUBLES
+ *   a job list needs, -1 with a message for a list the entry point would refuse.
+ * One launch, one workgroup of 256 per job; no atomics, no allocation, no synchronisation - two calls give the same bits; capturable.
+ * A null pointer, a negative count or length, mode outside 0 / 1, hop < 1, a z_abs that is not a number >= 0, a job with n < 1, a
+ * region outside flat, an index outside its table, a target that is not a finite number > 0, workspace regions out of order or a
+ * workspace smaller than the list needs: non-zero with a message before anything is launched.  n_jobs == 0 returns 0 and launches
+ * nothing. */
+typedef struct {
+  int64_t off, n;                   /* the region: flat[off .. off + n) */
+  double target;                    /* the amplitude it shall have */
+  int32_t ev, tail;                 /* the SedtScapeEvent / SedtReverbTail record that takes the gain, -1: none */
+  int64_t ws_off;                   /* the job's first double in the workspace */
+} SedtRelevelJob;                   /* 40 bytes; sedt_sizeof index 19 */
+int64_t sedt_relevel_workspace(const SedtRelevelJob* jobs_host, int n_jobs, int mode, int hop);
+int sedt_relevel(const float* flat, int64_t flat_len, const SedtRelevelJob* jobs_host, const SedtRelevelJob* jobs_dev, int n_jobs, int mode,
+                 const double* coef, const double* hop_map, int hop, double z_abs, double* work, int64_t work_len, SedtScapeEvent* ev,
+                 int n_ev, SedtReverbTail* tails, int n_tails, double* level, int32_t* counts, int32_t* status, void* stream);
 /* sedt_mixup_targets: the LABEL half of mixup_label_unlabel (utilities/mixup.py:129-196; call site engine.py:150-153, between the
  * teacher and the student forward of semi_train) without leaving the device.  Set 1 = the labelled targets (flat tables as
  * sedt_match_targets reads them: lab1/lab_off1 [B1+1], box1/box_off1 [ns1+1], optional ratio1 aligned with lab1, optional split1 =

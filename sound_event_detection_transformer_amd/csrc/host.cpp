@@ -85,7 +85,7 @@ extern "C" int sedt_hungarian_batch(const float* cost, int nlayers, int nclips, 
 }
 
 // sizeof of the argument structs of the ABI, by index (0 SedtIgemm, 1 SedtReduceJob, 2 SedtSplitJob, 3 SedtPrefetch, 4 SedtCriterion,
-// 5 SedtMatch, 6 SedtChunk, 7 SedtBnJob, 8 SedtPackJob, 9 SedtFragJob, 10 SedtPoolAt, 11 SedtCopyJob, 12 SedtViewAug, 13 SedtScapeEvent, 14 SedtScapeBg, 15 SedtStretchJob, 16 SedtReverbJob, 17 SedtReverbTail, 18 SedtReverbBed; -1 otherwise): a binding checks its own mirror of each struct
+// 5 SedtMatch, 6 SedtChunk, 7 SedtBnJob, 8 SedtPackJob, 9 SedtFragJob, 10 SedtPoolAt, 11 SedtCopyJob, 12 SedtViewAug, 13 SedtScapeEvent, 14 SedtScapeBg, 15 SedtStretchJob, 16 SedtReverbJob, 17 SedtReverbTail, 18 SedtReverbBed, 19 SedtRelevelJob; -1 otherwise): a binding checks its own mirror of each struct
 // against the library it loaded (tests/test_abi_cpu.py does for lib.py / packing.py / optim.py) - field drift between the header and a
 // hand-written ctypes / numpy mirror is otherwise silent until a kernel reads garbage.
 extern "C" int sedt_sizeof(int which) {
@@ -109,6 +109,7 @@ extern "C" int sedt_sizeof(int which) {
     case 16: return (int)sizeof(SedtReverbJob);
     case 17: return (int)sizeof(SedtReverbTail);
     case 18: return (int)sizeof(SedtReverbBed);
+    case 19: return (int)sizeof(SedtRelevelJob);
     default: return -1;
   }
 }

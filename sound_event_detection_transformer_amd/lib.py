@@ -238,6 +238,8 @@ SIGNATURES = {
     'sedt_reverb_spectra': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _vp]),
     'sedt_reverb': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     'sedt_reverb_bed': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i64, _vp]),
+    'sedt_relevel_workspace': (_i64, [_vp, _i, _i, _i]),
+    'sedt_relevel': (_i, [_vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _i, _d, _vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'sedt_mixup': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
     'sedt_mixup_targets': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'sedt_mixup_plan': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

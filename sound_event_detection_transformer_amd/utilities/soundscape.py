@@ -21,8 +21,8 @@ The plan.  ``draw`` consumes np.random clip by clip, in this order (a seed fixes
     if time_stretch is given - both stored as float32 in the plan's ``fx``; n = the largest excerpt whose final length
     m = floor(n f + 0.5) fits min(len_src f, max_event_samples, window); src_start as above; onset = randint(window - m + 1).  With both
     None nothing new is drawn: the plan of a seed is the plan it always was.  ``mix`` runs the effects on the device (sedt_stretch)
-    into a buffer behind the bank and hands the unchanged mixing call one more source per transformed event; an event's gain stays
-    what its SOURCE's staged level gives (the level is not measured again after the effect).
+    into a buffer behind the bank and hands the unchanged mixing call one more source per transformed event; without ``relevel`` an
+    event's gain stays what its SOURCE's staged level gives.
 Gains are computed in float64 and stored as float32: g_bg = 10^(ref_db / 20) / rms_bg (1 for a silent background),
 g_ev = 10^((ref_db + snr) / 20) / rms_src, the RMS taken over the WHOLE source - the default, ``level='rms'``.  With ``level='lufs'``
 the reference is the source's BS.1770 loudness L as Scaper's is (utilities/loudness.py, measured on the device when the source is
@@ -37,8 +37,16 @@ of an event.
     the stretch stage, over the wet events: a wet event's first m samples (the head) go to the mixing call as the event - same onset,
     class and gain, fade 0, the stage applied the fades to the dry sound - so the annotations stay those of the dry event; its last
     L - 1 samples (the tail) are laid, with the event's gain, over the clip's background in a bed row of ``window`` samples
-    (sedt_reverb_bed) that becomes the clip's background record (row, 0, 1.0).  The wet level is not measured again, backgrounds stay
-    dry, and the tail past the window's end is cut.
+    (sedt_reverb_bed) that becomes the clip's background record (row, 0, 1.0).  Backgrounds stay dry, and the tail past the window's
+    end is cut.
+    With ``relevel=True`` (the constructor's default, or ``mix(plan, relevel=)``) the level of every event is measured AFTER its effects,
+    as the generators do (utilities/relevel.py, sedt_relevel: ONE launch behind the stretch and reverb stages, nothing read back): the
+    region is the whole wet row of a wet event (n + L - 1 samples; the fades are in it), the row of m samples of a stretched one, the
+    bank excerpt [src_start, src_start + n) of any other - the fades of dry and stretched events are not part of the measurement.  The
+    gain float32(target / sqrt(level)) replaces the host's in the DEVICE records of the event and of its tail, target_db = ref_db + snr
+    per event (the plan's ``target_db``; draw_plan always fills it and consumes no randomness for it).  A region that is silent or
+    under the absolute gate keeps the host's gain (``last_relevel``: the stage's level, counts and status on the device).  Backgrounds
+    loop from a random start, so their whole-source level stays the right one; the peak limit and the targets are untouched.
 
 ``draw_plan``, ``make_plan``, ``gains`` and the record dtypes are the host half and need no GPU."""
 import math
@@ -65,14 +73,16 @@ class SoundscapePlan(object):
     ``ev_off`` int32 [B + 1] - clip b's events are ev[ev_off[b]:ev_off[b + 1]], mixed in that order.  ``fx``: None (no effects) or FX [E],
     the pitch shift and duration factor of every event; an event's ``n`` is then the length of its EXCERPT, and it occupies
     floor(n factor + 0.5) samples of the clip from ``onset`` on.  ``rir``: None (all dry) or int32 [E], the room impulse response every
-    event is convolved with, -1: dry"""
+    event is convolved with, -1: dry.  ``target_db``: None or float64 [E], the level every event shall have in the clip - ref_db + snr, in
+    dB of its RMS or in LUFS as the bank's ``level`` says; read only when the plan is mixed with ``relevel``"""
 
-    def __init__(self, bg, ev, ev_off, fx=None, rir=None):
+    def __init__(self, bg, ev, ev_off, fx=None, rir=None, target_db=None):
         self.bg = np.ascontiguousarray(bg, BACKGROUND)
         self.ev = np.ascontiguousarray(ev, EVENT)
         self.ev_off = np.ascontiguousarray(ev_off, np.int32)
         self.fx = None if fx is None else np.ascontiguousarray(fx, FX)
         self.rir = None if rir is None else np.ascontiguousarray(rir, np.int32)
+        self.target_db = None if target_db is None else np.ascontiguousarray(target_db, np.float64)
         B = self.bg.shape[0]
         if self.bg.shape != (B,) or self.ev_off.shape != (B + 1,) or self.ev.ndim != 1:
             raise ValueError('SoundscapePlan: bg [B], ev [E], ev_off [B + 1]')
@@ -80,6 +90,8 @@ class SoundscapePlan(object):
             raise ValueError('SoundscapePlan: fx [E], one (semitones, factor) per event')
         if self.rir is not None and self.rir.shape != self.ev.shape:
             raise ValueError('SoundscapePlan: rir [E], one response index per event (-1: dry)')
+        if self.target_db is not None and self.target_db.shape != self.ev.shape:
+            raise ValueError('SoundscapePlan: target_db [E], one level per event')
         if self.ev_off[0] != 0 or self.ev_off[-1] != self.ev.shape[0] or bool((np.diff(self.ev_off) < 0).any()):
             raise ValueError('SoundscapePlan: ev_off is not the exclusive scan of the clips\' event counts')
         if B and int(np.diff(self.ev_off).max()) > L.SCAPE_MAXEV:
@@ -120,12 +132,13 @@ def check_bank_loudness(what, lufs, classes):
                              'sound needs a loudness to be placed at an SNR')
 
 
-def make_plan(backgrounds, events, rirs=None):
+def make_plan(backgrounds, events, rirs=None, levels=None):
     """a SoundscapePlan from hand-made records: ``backgrounds`` one entry per clip, None or (src, start, gain); ``events`` one list per
     clip of (src, cls, src_start, n, onset, gain, fade) or, with effects, (src, cls, src_start, n, onset, gain, fade, semitones,
     factor) - the plan has ``fx`` as soon as one event has the two trailing fields, the others are the identity.  Nothing but the
     shape and the event count per clip is checked here: a record outside the bank raises the clip's status on the device.
-    ``rirs``: None, or one list per clip with one response index per event (-1: dry) - the plan's ``rir``."""
+    ``rirs``: None, or one list per clip with one response index per event (-1: dry) - the plan's ``rir``.  ``levels``: None, or one
+    list per clip with the level in dB / LUFS every event shall have in the clip - the plan's ``target_db``."""
     if len(backgrounds) != len(events):
         raise ValueError('make_plan: one background entry and one event list per clip')
     bg = np.zeros(len(backgrounds), BACKGROUND)
@@ -146,7 +159,12 @@ def make_plan(backgrounds, events, rirs=None):
         if len(rirs) != len(events) or any(len(r) != len(c) for r, c in zip(rirs, events)):
             raise ValueError('make_plan: rirs holds one list per clip, one response index per event')
         rir = np.asarray([int(i) for r in rirs for i in r], np.int32)
-    return SoundscapePlan(bg, ev, off.astype(np.int32), fx, rir)
+    target_db = None
+    if levels is not None:
+        if len(levels) != len(events) or any(len(l) != len(c) for l, c in zip(levels, events)):
+            raise ValueError('make_plan: levels holds one list per clip, one level per event')
+        target_db = np.asarray([float(v) for l in levels for v in l], np.float64)
+    return SoundscapePlan(bg, ev, off.astype(np.int32), fx, rir, target_db)
 
 
 def is_identity(fx):
@@ -206,7 +224,7 @@ def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), 
     fade = int(round(float(fade_seconds) * sr))
     bg = np.zeros(int(B), BACKGROUND)
     bg['src'] = -1
-    ev, fx, rir, off = [], [], [], [0]
+    ev, fx, rir, target_db, off = [], [], [], [], [0]
     for b in range(int(B)):
         if background:
             s = int(backgrounds[np.random.randint(len(backgrounds))])
@@ -234,9 +252,11 @@ def draw_plan(B, lens, rms, by_class, backgrounds, window, sr, n_events=(1, 9), 
             src_start = np.random.randint(int(lens[s]) - n + 1)
             onset = np.random.randint(window - m + 1)
             ev.append((s, c, src_start, n, onset, gains(ref_db, snr, rms[s]), fade))
+            target_db.append(np.float64(ref_db) + np.float64(snr))
         off.append(len(ev))
     return SoundscapePlan(bg, np.array(ev, EVENT) if ev else np.zeros(0, EVENT), np.asarray(off, np.int32),
-                          np.array(fx, FX).reshape(-1) if effects else None, np.asarray(rir, np.int32) if wet_draws else None)
+                          np.array(fx, FX).reshape(-1) if effects else None, np.asarray(rir, np.int32) if wet_draws else None,
+                          np.asarray(target_db, np.float64))
 
 
 class SoundscapeClips(object):
@@ -247,12 +267,13 @@ class SoundscapeClips(object):
     scaled down to it; level: 'rms' - ref_db and snr_db refer to the sources' RMS - or 'lufs' - to their BS.1770 loudness, measured on
     the device at staging (``lufs``, ``level_amp`` = 10^(lufs / 20) per source); stretch_n_fft: the frame length of the effects' phase
     vocoder (512, 1024 or 2048; the resampling filter is ``resample_quality``'s); reverb_n_fft: the frame length of the reverberation's
-    partitioned convolution (512, 1024 or 2048).  See the module docstring."""
+    partitioned convolution (512, 1024 or 2048); relevel: measure every event's level after its effects, on the device, before it is
+    mixed (``mix``'s default; the plan needs ``target_db``).  See the module docstring."""
 
     STATUS_REASONS = STATUS_REASONS
 
     def __init__(self, mel, labels, window_seconds=10.0, max_targets=32, min_event_seconds=0.0, collapse=True, peak_limit=1.0,
-                 device='cuda', resample_quality='kaiser_best', level='rms', stretch_n_fft=2048, reverb_n_fft=2048):
+                 device='cuda', resample_quality='kaiser_best', level='rms', stretch_n_fft=2048, reverb_n_fft=2048, relevel=False):
         self.mel, self.labels = mel, list(labels)
         self.window_seconds = float(window_seconds)
         self.window = int(round(self.window_seconds * mel.sr))
@@ -282,6 +303,7 @@ class SoundscapeClips(object):
         self.stretch_n_fft, self._stretch, self._fx_buf, self._fx_bank = int(stretch_n_fft), None, None, None
         self.last_fx = self.last_fx_status = self.last_rv_status = None
         self.reverb_n_fft, self._reverb, self.rooms, self._room_ids = int(reverb_n_fft), None, [], []
+        self.relevel, self._relevel, self._relevel_out, self.last_relevel = bool(relevel), None, None, None
 
     # ------------------------------------------------------------------ staging
     def resampler(self, rate):
@@ -402,10 +424,10 @@ class SoundscapeClips(object):
         return draw_plan(B, self.ns, level, self.by_class, self.backgrounds, self.window, self.mel.sr, n_events, snr_db, ref_db,
                          max_event_seconds, fade_seconds, background, pitch_shift, time_stretch, reverb, self.rooms)
 
-    def plan(self, backgrounds, events, rirs=None):
+    def plan(self, backgrounds, events, rirs=None, levels=None):
         """a SoundscapePlan from hand-made records (make_plan); class names in the events' second field are looked up"""
         events = [[(e[0], self._class_index(e[1]) if isinstance(e[1], str) else e[1]) + tuple(e[2:]) for e in clip] for clip in events]
-        return make_plan(backgrounds, events, rirs)
+        return make_plan(backgrounds, events, rirs, levels)
 
     # ------------------------------------------------------------------ batches
     def buffers(self, B):
@@ -497,6 +519,32 @@ class SoundscapeClips(object):
                     rows_len=np.concatenate([rows_len, totals, np.full(len(clips), self.window)]).astype(np.int64),
                     samples=int(bed_off[-1]) + self.window, floats=floats)
 
+    def releveler(self):
+        """the DeviceRelevel of the plans mixed with ``relevel`` (the bank's ``level``), made at first use"""
+        if self._relevel is None:
+            from .relevel import DeviceRelevel
+            self._relevel = DeviceRelevel(self.mel.sr, self.level, device=self.dev)
+        return self._relevel
+
+    def _relevel_records(self, plan, ev, rows_off, rows_len, rvb):
+        """the host half of a plan's relevel stage: (SedtRelevelJob records, the doubles of workspace), one job per valid event in plan
+        order.  ``ev``: the events after the stretch and reverb stages' rewrites; ``rows_off`` / ``rows_len``: the source table they
+        index; ``rvb``: _reverb_records' dict or None.  A wet event's region is its whole wet row and its gain also goes to its tail
+        record; any other event's region is ev's own (src, src_start, n) - the stretched row or the bank excerpt.  An event whose
+        record does not lie inside the table gets no job: sedt_soundscape raises its clip's status."""
+        rl = self.releveler()
+        n_rows = len(rows_len)
+        src = np.clip(ev['src'], 0, n_rows - 1)
+        inside = (ev['src'] >= 0) & (ev['src'] < n_rows) & (ev['src_start'] >= 0) & (ev['n'] >= 1) & (ev['src_start'] <= rows_len[src]) & \
+            (ev['n'] <= rows_len[src] - ev['src_start'])
+        todo = np.flatnonzero(inside)
+        offs, ns = rows_off[src[todo]] + ev['src_start'][todo], ev['n'][todo].astype(np.int64)
+        tail = np.full(len(todo), -1, np.int64)
+        if rvb is not None:                                          # a wet event: src is its wet row, n its head; measure the whole row
+            k = np.searchsorted(todo, rvb['wet'])
+            ns[k], tail[k] = rows_len[ev['src'][rvb['wet']]], np.arange(len(rvb['wet']))
+        return rl.jobs(offs, ns, plan.target_db[todo], ev=todo, tails=tail)
+
     def _effect_buffer(self, samples):
         """the f32 device buffer that holds the bank and, behind it, the transformed sounds of one batch: the bank is copied into it
         once (again after add_events / add_backgrounds, or when a batch needs more room than any before it)"""
@@ -508,7 +556,7 @@ class SoundscapeClips(object):
             self._fx_bank = self.flat
         return self._fx_buf
 
-    def mix(self, plan, status=None):
+    def mix(self, plan, status=None, relevel=None):
         """ONE sedt_soundscape call on the current stream into this object's buffers: (wave (B, window) f32 on the device, samples per
         clip - the window - as a host list, DeviceTargets).  The records travel through a ring of pinned buffers; nothing synchronises.
         A plan with effects (``fx``) runs sedt_stretch first, over its events that are not the identity: their results lie behind a
@@ -519,11 +567,21 @@ class SoundscapeClips(object):
         excerpt - and sedt_reverb_bed over the clips that hold one (module docstring); the table grows by the wet rows and the bed rows,
         every record travels in the same pinned upload, and ``last_fx`` also reports the reverb jobs, tails and beds
         (``last_rv_status``: the stage's statuses).  A plan without ``rir``, or with nothing but -1, issues the calls of before.
+        ``relevel`` (None: the constructor's) then issues ONE sedt_relevel launch over all valid events, behind the stretch and reverb
+        stages and before sedt_reverb_bed and sedt_soundscape (module docstring): the job list travels in the same pinned upload,
+        ``last_fx`` reports the jobs (``relevel_jobs``; ``ev_dev`` / ``tails_dev``: the device records the gains went to) and
+        ``last_relevel`` holds the stage's (level, counts, status) on the device, in buffers of this object's that every mix reuses.  A
+        plan without ``target_db`` is refused.  With relevel off the calls and the bytes are those of before.
         ``status``: an int32 [B] device tensor to raise the statuses in instead of the buffer's own (a row of a log,
         engine.train_on_recordings).  ``last_peak`` / ``last_scale`` are the clips' peaks before scaling and their scales, on the device."""
         if self.table is None:
             raise RuntimeError('SoundscapeClips.mix: add_events() / add_backgrounds() first')
         B, E = len(plan), int(plan.ev.shape[0])
+        relevel = self.relevel if relevel is None else bool(relevel)
+        if relevel and plan.target_db is None:
+            raise ValueError('SoundscapeClips.mix: relevel asked for, the plan has no target_db: draw() fills it, plan(..., levels=) takes it')
+        if relevel and not bool(np.isfinite(plan.target_db).all()):
+            raise ValueError('SoundscapeClips.mix: relevel asked for, the plan\'s target_db holds a level that is not finite')
         if not 1 <= B <= L.SCAPE_MAXB:
             raise ValueError(f'SoundscapeClips.mix: 1 .. {L.SCAPE_MAXB} clips per call')
         if self._ring is None:
@@ -538,10 +596,11 @@ class SoundscapeClips(object):
         if plan.rir is not None and E and bool((plan.rir >= 0).any()):
             rvb = self._reverb_records(plan, *((plan.ev, self.src_off[:-1], np.asarray(self.ns, np.int64), int(self.src_off[-1]))
                                                if fx is None else (fx[0], fx[2], fx[3], fx[4])))
-        self.last_fx = None
+        self.last_fx = self.last_relevel = None
         bg = plan.bg
         if fx is None and rvb is None:                               # no effects: the call and the bytes of a plan without ``fx`` / ``rir``
             flat, flat_len, n_src, tail = self.flat, int(self.src_off[-1]), len(self.ns), []
+            rows_off, rows_len = self.src_off[:-1], np.asarray(self.ns, np.int64)
         else:
             from .stretch import JOB as STRETCH_JOB
             jobs, floats = (np.zeros(0, STRETCH_JOB), 0) if fx is None else (fx[1], fx[5])
@@ -554,7 +613,14 @@ class SoundscapeClips(object):
                     rows_off.view(np.uint8), rows_len.view(np.uint8), jobs.view(np.uint8)]
             if rvb is not None:
                 tail += [rvb['jobs'].view(np.uint8), rvb['tails'].view(np.uint8), rvb['beds'].view(np.uint8)]
-        raw = self._ring.upload(np.concatenate([bg.view(np.uint8), ev.view(np.uint8), plan.ev_off.view(np.uint8)] + tail))
+        rl = self._relevel_records(plan, ev, rows_off, rows_len, rvb) if relevel and E else None
+        if rl is not None and not len(rl[0]):
+            rl = None
+        extra = []
+        if rl is not None:                                           # the job list behind everything else, on a multiple of 8 bytes
+            head = BACKGROUND.itemsize * B + EVENT.itemsize * ev.shape[0] + 4 * (B + 1) + sum(t.size for t in tail)
+            extra = [np.zeros(-head % 8, np.uint8), rl[0].view(np.uint8)]
+        raw = self._ring.upload(np.concatenate([bg.view(np.uint8), ev.view(np.uint8), plan.ev_off.view(np.uint8)] + tail + extra))
         n_bg, n_ev = BACKGROUND.itemsize * B, EVENT.itemsize * ev.shape[0]
         d_bg, d_ev, d_off = raw[:n_bg], raw[n_bg:n_bg + n_ev], raw[n_bg + n_ev:n_bg + n_ev + 4 * (B + 1)]
         t_off, t_len = self.table['off'], self.table['len']
@@ -574,10 +640,18 @@ class SoundscapeClips(object):
                 self.last_rv_status = rv.launch(flat, rj, flat, rv.workspace(rvb['floats']), jobs_dev=raw[o:o + rj.nbytes])
                 d_tails = raw[o + rj.nbytes:o + rj.nbytes + tails.nbytes]
                 d_beds = raw[o + rj.nbytes + tails.nbytes:o + rj.nbytes + tails.nbytes + beds.nbytes]
+                if rl is not None:                                   # behind sedt_reverb, before the tails' gains are read
+                    self._relevel_launch(flat, flat_len, rl, raw, head + extra[0].size, d_ev, ev.shape[0], d_tails, len(tails))
                 L.check(L.load().sedt_reverb_bed(L.p(flat), flat_len, L.p(t_off), L.p(t_len), n_src, L.p(d_beds), len(beds), L.p(d_tails),
                                                  len(tails), self.window, L.p(flat), flat_len, L.stream_ptr()), 'reverb_bed')
                 self.last_fx.update(reverb_jobs=rj, tails=tails, beds=beds, bg=bg, wet=rvb['wet'], clips=rvb['clips'],
                                     rows_off=rows_off, rows_len=rows_len, reverb_workspace=rv.workspace(rvb['floats']))
+        if rl is not None and rvb is None:
+            self._relevel_launch(flat, flat_len, rl, raw, head + extra[0].size, d_ev, ev.shape[0], None, 0)
+        if rl is not None:
+            if self.last_fx is None:
+                self.last_fx = dict(events=ev, flat=flat)
+            self.last_fx.update(relevel_jobs=rl[0], ev_dev=d_ev, tails_dev=d_tails if rvb is not None else None)
         L.check(L.load().sedt_soundscape(L.p(flat), flat_len, L.p(t_off), L.p(t_len), n_src, L.p(d_bg), L.p(d_ev), L.p(d_off), B,
                                          self.window, self.mel.sr, self.max_targets,
                                          self.min_event_seconds, int(self.collapse), self.peak_limit, L.p(wave), L.p(part), L.p(peak),
@@ -585,15 +659,23 @@ class SoundscapeClips(object):
         self.last_peak, self.last_scale = peak, scale
         return wave, [self.window] * B, DeviceTargets(blob, status, B, self.max_targets, ['soundscape'] * B, self.window_seconds)
 
-    def batch(self, transform, plan=None, B=None, status=None):
+    def _relevel_launch(self, flat, flat_len, rl, raw, o, d_ev, n_ev, d_tails, n_tails):
+        stage, E = self.releveler(), len(rl[0])
+        if self._relevel_out is None or self._relevel_out[0].shape[0] < E:          # zeroed once; a job the device refuses leaves its row
+            self._relevel_out = stage.outputs(2 * E)
+        out = tuple(t[:E] for t in self._relevel_out)
+        self.last_relevel = stage.launch(flat, rl[0], ev=d_ev, n_ev=n_ev, tails=d_tails, n_tails=n_tails, workspace=stage.workspace(rl[1]),
+                                         jobs_dev=raw[o:o + rl[0].nbytes], flat_len=flat_len, out=out)
+
+    def batch(self, transform, plan=None, B=None, status=None, relevel=None):
         """mix -> mel -> transform: (x (B, 1, frames, n_mels), DeviceTargets).  ``plan``: a SoundscapePlan, else draw(B).  The transform
         (a DeviceBoxTransform) may augment; a DeviceViewTransform makes both views of the mean-teacher recipe and the result is
-        ((x_teacher, x_student), DeviceTargets)."""
+        ((x_teacher, x_student), DeviceTargets).  ``relevel``: mix's (None: the constructor's)."""
         if plan is None:
             if B is None:
                 raise ValueError('SoundscapeClips.batch: plan= or B=')
             plan = self.draw(B)
-        wave, lengths, targets = self.mix(plan, status=status)
+        wave, lengths, targets = self.mix(plan, status=status, relevel=relevel)
         amp = self._amp.get(wave.shape[0])
         if amp is None:
             amp = self._amp[wave.shape[0]] = torch.zeros((wave.shape[0], 1 + self.window // self.mel.hop, self.mel.F), dtype=torch.float32,
